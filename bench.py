@@ -5,14 +5,20 @@ A "step" is one time step of ver7/GSimulation.cpp:138-200 over all n bodies: the
 kernel, the Euler update and the kinetic-energy partials (plus, at N > 1, the all-gather of the
 position blocks).  State is resident in HBM before the timed region starts.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Workload: N == 1 -> BASELINE.json configs[2] (n = 262144, fp32: the roofline configuration the metric's
 target is quoted on); N > 1 -> configs[3] (n = 1048576 block-partitioned over the N ranks, one RCCL
 all-gather of the positions per step).  Prints ONE JSON line on rank 0.
 
-An N > 1 line validates itself (all outside the timed region): `parity` = the same sharded simulation restarted
+A plain run sets up, warms up, times the K steps and prints the line: the headline figure and what the timed
+steps themselves recorded (ms_per_step, kenergy_after_run, the HIP-event roofline of the force launches).
+--dump-outputs DIR writes what the last timed step left a caller (dump_outputs).  Everything that takes runs of
+its own -- CPU baselines, parity against the reference's traces, the other summation order, the slice proxies and
+the N > 1 legs below -- runs only with --full.
+
+With --full, an N > 1 line validates itself (all outside the timed region): `parity` = the same sharded simulation restarted
 from the seed-42 state, 10 steps against the reference's own trace; `ranks` = force-kernel and all-gather times
 of every rank (min / mean / max, skew, bytes, devices); and the PRODUCT's own two multi-GPU forms run on the same
 GPUs, timed and compared with the torch.distributed figure: `native_single_process` = one nbody.x driving all N
@@ -22,7 +28,7 @@ in-place ncclAllGather inside libnbx; `value_native_rank_group`).  The N > 1 lin
 a scaling record: `cpu_baseline` (rank 0, before it touches the GPU) and `one_gpu_at_multi_gpu_n` (rank 0's GPU
 alone at the same n, the other ranks idle at a barrier).
 
-An N = 1 line carries `multi_gpu_slice_proxy`: what ONE rank of 2 / 4 / 8 computes per step at n = 262144, 524288 and
+With --full, an N = 1 line carries `multi_gpu_slice_proxy`: what ONE rank of 2 / 4 / 8 computes per step at n = 262144, 524288 and
 1048576 on this one GPU, next to the one-GPU step at the same n: the multi-GPU speed-up before communication and skew.
 """
 import argparse
@@ -387,6 +393,36 @@ def native_single_process_check(dist, rank, world, n, precision, ke_torch_path, 
 
 LOOP_NAMES = {1: "cxx", 2: "asm", 3: "asm_ts", 4: "asm_pf"}
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6  # the data; the .npy headers stay well inside 64 MB
+DUMP_FIELDS = ("pos_x", "pos_y", "pos_z", "vel_x", "vel_y", "vel_z")
+
+
+def dump_outputs(out_dir, sim, ke, dist, rank):
+    """--dump-outputs: the state the timed steps left a caller of the path -- positions and velocities of all n bodies as
+    nbx_download returns them, in the run's precision -- and the kinetic energy after the last step (float64), one
+    DIR/<name>.npy each.  Above DUMP_LIMIT_BYTES the bodies are a fixed sample (seeded, sorted indices: the same in every run).
+    Collective at N > 1: a rank holds all positions but only its own slice of the velocities, so the slices go to rank 0."""
+    import numpy as np
+    state = sim.engine.download()
+    if sim.dist:
+        sl = slice(sim.i_begin, sim.i_begin + sim.i_count)
+        parts = [None] * sim.world
+        dist.all_gather_object(parts, (sim.i_begin, sim.i_count, [state[f][sl] for f in DUMP_FIELDS[3:]]))
+        for b, c, vs in parts:
+            for f, v in zip(DUMP_FIELDS[3:], vs):
+                state[f][b:b + c] = v
+    if rank != 0:
+        return
+    n = sim.n
+    per_body = sum(state[f].itemsize for f in DUMP_FIELDS)
+    idx = None
+    if n * per_body + 8 > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(42).choice(n, (DUMP_LIMIT_BYTES - 8) // per_body, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for f in DUMP_FIELDS:
+        np.save(os.path.join(out_dir, f + ".npy"), state[f] if idx is None else state[f][idx])
+    np.save(os.path.join(out_dir, "kenergy.npy"), np.array([ke], dtype=np.float64))
+
 
 def ran_shape(st):
     """The launch shape in the vocabulary of profiles/roofline_traffic.json's `profiled_shape` (tools/roofline_summary.py)."""
@@ -408,7 +444,14 @@ def main():
     ap.add_argument("--kernel", default="auto", choices=("auto", "lds", "sgpr", "sgprw", "jlane"))
     ap.add_argument("--order", default="auto", choices=("auto", "reference", "tree"),
                     help="summation order of a body's pair terms (include/nbx.h): reference = the CPU loop's order")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the final positions, velocities and kinetic energy as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baselines, parity against the reference's traces, "
+                         "the other summation order, the multi-GPU slice proxies and, at N > 1, the per-rank breakdown and native legs")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # stdout carries ONE JSON line and nothing else: native libraries write there too (RCCL prints a version banner on
     # rank 0 at communicator creation), so file descriptor 1 points at stderr until the line is ready
@@ -431,7 +474,7 @@ def main():
 
     # CPU baseline first: it may start a child process, so it runs before this process touches the GPU
     cpu = cpu_o3 = None
-    if rank == 0 and a.cpu_baseline != "none":  # N > 1 too: a scaling record then carries its own CPU denominator
+    if a.full and rank == 0 and a.cpu_baseline != "none":  # N > 1 too: a scaling record then carries its own CPU denominator
         cpu = cpu_baseline(a.cpu_baseline, n, a.precision)
         # SURVEY.md 8d asks for both builds of the reference: the pinned -O2 one above (the oracle's flags) and a best-effort one
         if cpu["kind"] == "reference" and a.precision == 32 and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "ver7_trace_o3.x")):
@@ -457,7 +500,7 @@ def main():
     opts = dict(bodies_per_lane=a.bodies_per_lane, j_split=a.j_split, summation_order={"auto": 0, "reference": 1, "tree": 2}[a.order],
                 kernel_variant={"auto": 0, "lds": 1, "sgpr": 2, "sgprw": 3, "jlane": 6}[a.kernel])
 
-    parity = parity_probe(nbx, n, a.precision, full=bool(a.n)) if (rank == 0 and not use_dist) else None  # N > 1: parity_probe_sharded below
+    parity = parity_probe(nbx, n, a.precision, full=bool(a.n)) if (a.full and rank == 0 and not use_dist) else None  # N > 1: parity_probe_sharded below
 
     ic = nbx.initial_conditions(n, a.precision)  # synthetic: the reference's seed-42 generator
     sim = sharded.ShardedSimulation(n, a.precision, dist=dist if use_dist else None, force_collective=force_dist, **opts)
@@ -484,10 +527,12 @@ def main():
         elapsed = float(t.item())
     st = sim.engine.ctx.stats()
     ke = sim.kenergy()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, sim, ke, dist, rank)  # before anything below steps the simulation on
 
     # N > 1: what every rank did, gathered to rank 0 -- a sub-6x result must be diagnosable from the line alone
     breakdown = native = native_single = same_n_multi = None
-    if use_dist:
+    if a.full and use_dist:
         # the all-gathers are timed in a pass of their own, AFTER the timed region (two event records per step inside
         # the headline's clock were small but unmeasured): the same number of steps, events on the stream the kernel and the
         # collective are ordered on
@@ -530,7 +575,7 @@ def main():
     same_n = None
     rank8 = rank4 = rank2 = None
     other_order = None
-    if world == 1 and a.order == "auto" and not a.j_split and a.kernel in ("auto",):
+    if a.full and world == 1 and a.order == "auto" and not a.j_split and a.kernel in ("auto",):
         # the same workload with the OTHER summation order (see DESIGN.md "Summation order"): reference order is what
         # matches CPU ver7's kenergy at this size, tree order is the fastest and the closest to an fp64 sum
         alt = 2 if st["summation_order"] == 1 else 1
@@ -550,7 +595,7 @@ def main():
                        "j_split": st2["j_split"]}
         s2.close()
     proxy = None
-    if world == 1 and not a.n and a.precision == 32:
+    if a.full and world == 1 and not a.n and a.precision == 32:
         # What ONE rank of the 2-, 4- and 8-GPU forms computes per step at n = 262144, 524288 and 1048576 (configs[3]) -- its block of the
         # partition against all resident records -- on this GPU, next to one GPU stepping all n bodies: the P-GPU speed-up over one GPU at
         # the same n, before communication and skew, is the ratio of the two (at n = 1M, P = 8 the all-gather is 2 MiB sent / 14 MiB
@@ -658,8 +703,9 @@ def main():
             # the three ways this job can be run, side by side: torch.distributed driving libnbx (the timed region above), the product's
             # single-process group (one host thread, all GPUs) and the product's one-process-per-GPU group
             line["value_torch_distributed"] = value
-            line["value_native_single_process"] = (native_single or {}).get("pair_per_s")
-            line["value_native_rank_group"] = (native or {}).get("pair_per_s")
+            if a.full:  # the native legs ran (a null value: skipped or failed, the leg's record says which)
+                line["value_native_single_process"] = (native_single or {}).get("pair_per_s")
+                line["value_native_rank_group"] = (native or {}).get("pair_per_s")
         if native_single:
             line["native_single_process"] = native_single
         if proxy:

@@ -53,3 +53,29 @@ def test_divergence_curve_of_the_two_reference_builds(bench):
     assert abs(d["printed_rows"]["450"]["second_build_vs_pinned_build"] - 1.285e-4) < 2e-6  # SURVEY G2's 1.3e-4
     assert d["printed_rows"]["50"]["second_build_vs_pinned_build"] < 1e-6 and sorted(map(int, d["printed_rows"])) == list(range(50, 501, 50))
     assert 150 < d["first_step_above_1e-5"]["second_build_vs_pinned_build"] < 300
+
+
+def test_dump_outputs_samples_a_fixed_subset_above_the_limit(bench, tmp_path, monkeypatch):
+    """--dump-outputs above DUMP_LIMIT_BYTES: the same seeded, sorted sample of bodies in every run and in every array, within the
+    limit; below it every body."""
+    import numpy as np
+
+    class Engine:
+        def download(self):
+            return {f: np.arange(1000, dtype=np.float32) * (k + 1) for k, f in enumerate(bench.DUMP_FIELDS)}
+
+    class Sim:
+        n, engine, dist = 1000, Engine(), None
+
+    bench.dump_outputs(str(tmp_path / "all"), Sim(), 2.5, None, 0)
+    assert np.array_equal(np.load(tmp_path / "all" / "vel_z.npy"), np.arange(1000, dtype=np.float32) * 6)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 24 * 100 + 8)  # room for 100 of the 1000 bodies
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), Sim(), 2.5, None, 0)
+    idx = np.load(tmp_path / "a" / "pos_x.npy").astype(np.int64)
+    assert len(idx) == 100 and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < 1000
+    for k, f in enumerate(bench.DUMP_FIELDS):
+        a, b = np.load(tmp_path / "a" / (f + ".npy")), np.load(tmp_path / "b" / (f + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, b) and np.array_equal(a, idx.astype(np.float32) * (k + 1))
+    assert sum(os.path.getsize(tmp_path / "a" / (f + ".npy")) - 128 for f in bench.DUMP_FIELDS) <= bench.DUMP_LIMIT_BYTES
+    assert np.load(tmp_path / "a" / "kenergy.npy").tolist() == [2.5]

@@ -1,12 +1,12 @@
-"""Drop-in proof (build container only: skipped where /root/reference does not exist, e.g. on the GPU box).
+"""Drop-in proof (skipped where oracle/_ref was not built, i.e. where the reference's sources are not at hand).
 
 The reference's OWN, unmodified callers -- ver7/main.cpp, ver8/main.cpp (ver7/main.cpp:25-46) and ver5_all/main.cpp
 (:23-66, which needs init_mpi(), world_rank and the <iostream>/<string> its GSimulation.hpp provides,
 ver5_all/GSimulation.hpp:25-30,60-65) -- are compiled against host/GSimulation.{hpp,cpp} + libnbx and run.
 
-The sources are read where they lie, at compile time only: each main.cpp is fed to g++ on stdin, so its
-`#include "GSimulation.hpp"` cannot resolve to the header next to it and must find host/GSimulation.hpp through -I
-(checked with -H).  Nothing of the reference is copied into the repo and no binary built here travels.
+`make -C oracle ref` (build()) compiles each main.cpp, fed to g++ on stdin, into oracle/_ref/<version>_main.o, so its
+`#include "GSimulation.hpp"` cannot resolve to the header next to it and must find host/GSimulation.hpp through -I; the
+headers it reached are recorded beside the object by -H.  Nothing of the reference is copied into the repo.
 """
 import os
 import subprocess
@@ -15,26 +15,24 @@ import pytest
 
 from conftest import PKG, ROOT, has_gpu
 
-REF = "/root/reference"
+REF_BUILD = os.path.join(ROOT, "oracle", "_ref")
 HOST = os.path.join(PKG, "host")
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "ver7")), reason="the reference sources exist only in the build container")
-
 MAINS = [("ver7", []), ("ver8", []), ("ver5_all", ["-DNBX_BANNER_IN_MAIN"])]
+pytestmark = pytest.mark.skipif(not all(os.path.exists(os.path.join(REF_BUILD, v + "_main.o")) for v, _ in MAINS),
+                                reason="oracle/_ref is only built where the reference's sources exist")
 
 
 def _build(tmp_path, version, defs):
     if not os.path.exists(os.path.join(PKG, "libnbx.so")):
         subprocess.check_call(["make", "-s", "-C", ROOT, "lib"])
     exe = str(tmp_path / ("nbody_%s_main.x" % version))
-    obj = str(tmp_path / "main.o")
-    src = open(os.path.join(REF, version, "main.cpp")).read()
-    # main.cpp from stdin, cwd = an empty directory: the only GSimulation.hpp in reach is host/'s
-    p = subprocess.run(["g++", "-std=c++14", "-O2", "-H", "-x", "c++", "-", "-I", HOST, "-c", "-o", obj], input=src, text=True,
-                       capture_output=True, cwd=str(tmp_path))
-    assert p.returncode == 0, p.stderr
-    headers = [ln.split()[-1] for ln in p.stderr.splitlines() if ln.startswith(".")]
-    assert os.path.join(HOST, "GSimulation.hpp") in [os.path.normpath(h) for h in headers], headers
-    assert not any(os.path.normpath(h).startswith(REF) for h in headers), headers
+    obj = os.path.join(REF_BUILD, version + "_main.o")
+    with open(os.path.join(REF_BUILD, version + "_main.H")) as f:
+        headers = [os.path.normpath(os.path.join(REF_BUILD, ln.split()[-1])) for ln in f if ln.startswith(".")]
+    assert os.path.join(HOST, "GSimulation.hpp") in headers, headers
+    # every header of the drop-in's name set came from host/, none from beside the reference's main.cpp
+    own = set(os.listdir(HOST))
+    assert all(os.path.dirname(h) == HOST for h in headers if os.path.basename(h) in own), headers
     subprocess.check_call(["g++", "-std=c++14", "-O2"] + defs + [os.path.join(HOST, "GSimulation.cpp"), obj, "-o", exe,
                                                                   "-L" + PKG, "-lnbx", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"])
     return exe
