@@ -731,6 +731,8 @@ void nbx_destroy(nbx_ctx* c) {
   if (c->mass_all) (void)hipFree(c->mass_all);
   if (c->posm_pairs) (void)hipFree(c->posm_pairs);
   if (c->ke_dev) (void)hipFree(c->ke_dev);
+  if (c->diag_part) (void)hipFree(c->diag_part);
+  if (c->diag_dev) (void)hipFree(c->diag_dev);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }

@@ -85,6 +85,7 @@ struct nbx_group {
   std::vector<Rccl::comm_t> comm;    // RCCL path
   bool use_rccl = false;
   double* ke_all = nullptr;          // rank groups: [P] sum m v^2 of every rank, all-gathered
+  double* diag_all = nullptr;        // rank groups, nbx_group_diagnostics: [P][kDiagFields] raw sums of every rank, all-gathered
   void* vel_stage = nullptr;         // rank groups, nbx_group_download: own velocities padded to `block` records
   void* vel_all = nullptr;           //   and the all-gathered [P * block] records
   // watchdog bookkeeping (nbx_watchdog.hpp): steps enqueued since the last host synchronisation, and what one step took
@@ -607,6 +608,7 @@ void nbx_group_destroy(nbx_group* g) {
   for (size_t r = 0; r < g->done.size(); ++r) if (g->done[r]) { (void)hipSetDevice(g->dev[r]); (void)hipEventDestroy(g->done[r]); }
   if (!g->dev.empty()) (void)hipSetDevice(g->dev[0]);
   if (g->ke_all) (void)hipFree(g->ke_all);
+  if (g->diag_all) (void)hipFree(g->diag_all);
   if (g->vel_stage) (void)hipFree(g->vel_stage);
   if (g->vel_all) (void)hipFree(g->vel_all);
   for (nbx_ctx* c : g->rank) nbx_destroy(c);
@@ -749,6 +751,49 @@ int nbx_group_download(nbx_group* g, void* px, void* py, void* pz, void* vx, voi
     const int rc = nbx_download(g->rank[r], r == 0 ? px : nullptr, r == 0 ? py : nullptr, r == 0 ? pz : nullptr, vx, vy, vz);
     if (rc) return rc;
   }
+  return NBX_OK;
+  });
+}
+
+int nbx_group_diagnostics(nbx_group* g, nbx_diag_t* out) {
+  return guarded("nbx_group_diagnostics", [&]() -> int {
+  if (!g || !out) return fail(NBX_ERR_ARG, "nbx_group_diagnostics: NULL argument");
+  if (out->struct_size != 0 && out->struct_size != (int32_t)sizeof(nbx_diag_t))
+    return fail(NBX_ERR_ARG, "nbx_group_diagnostics: nbx_diag_t.struct_size does not match this library");
+  if (g->broken) return fail(NBX_ERR_STATE, "nbx_group_diagnostics: a retune failed while rebuilding the contexts; destroy the group");
+  if (!g->uploaded) return fail(NBX_ERR_STATE, "nbx_group_diagnostics: nbx_group_upload has not been called");
+  constexpr int F = kDiagFieldCount;
+  double sum[F] = {};
+  int32_t bodies = 0;
+  if (g->my_rank >= 0) {
+    // one process per GPU: every rank reduces its partials on the device, one all-gather of the raw sums, and all ranks add
+    // the P rows in rank order -- the same numbers on every rank (as the kinetic energy of nbx_group_step)
+    Watchdog::Scope bounded("nbx_group_diagnostics (all-gather of the partials: stream synchronisation)", queued_allowance(g));
+    struct Synced { nbx_group* g; ~Synced() { g->steps_unsynced = 0; } } synced{g};
+    nbx_ctx* c = g->rank[0];
+    int rc = enqueue_diagnostics(c, "nbx_group_diagnostics");
+    if (rc) return rc;
+    if (!g->diag_all) HIP_TRY(hipMalloc(&g->diag_all, sizeof(double) * F * (size_t)g->P));
+    const ncclResult_t e = g_rccl.AllGather(c->diag_dev, g->diag_all, sizeof(double) * F, ncclChar, g->comm[0], c->stream);
+    if (e != ncclSuccess) return rccl_fail("ncclAllGather(diagnostics)", e);
+    std::vector<double> rows((size_t)F * g->P);
+    HIP_TRY(hipMemcpyAsync(rows.data(), g->diag_all, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int r = 0; r < g->P; ++r)
+      for (int q = 0; q < F; ++q) sum[q] += rows[(size_t)r * F + q];
+    bodies = g->n;
+  } else {
+    for (nbx_ctx* c : g->rank) {  // rank order: deterministic
+      int rc = enqueue_diagnostics(c, "nbx_group_diagnostics");
+      if (rc) return rc;
+      double raw[F];
+      HIP_TRY(hipMemcpyAsync(raw, c->diag_dev, sizeof(raw), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      for (int q = 0; q < F; ++q) sum[q] += raw[q];
+      bodies += c->i_count;
+    }
+  }
+  diag_fill(sum, bodies, g->rank[0]->steps_done, out);
   return NBX_OK;
   });
 }

@@ -9,7 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/nbx.h"
+#include "../../include/nbx_diag.h"  // includes nbx.h
 
 namespace nbx_detail {
 
@@ -81,6 +81,9 @@ struct nbx_ctx {
   struct GraphUnit { int steps; int parity; double dt; hipGraphExec_t exec; };
   std::vector<GraphUnit> graphs;
   long long graph_replays = 0;
+  // diagnostics (nbx_diag.hip): per-workgroup partials and the reduced fields, allocated on first use
+  double* diag_part = nullptr;
+  double* diag_dev = nullptr;
 };
 
 namespace nbx_detail {
@@ -88,4 +91,10 @@ namespace nbx_detail {
 int use_device(nbx_ctx* c);
 double model_force_cost(const nbx_ctx* c, int own);  // relative cost of one force launch if the context owned `own` bodies (the tuner's predictor)
 int enqueue_ke_reduce(nbx_ctx* c, int slot);  // ke_part[0 .. ke_parts) -> ke_dev[slot], fixed order, on the context's stream
+constexpr int kDiagFieldCount = 9;  // = nbx::kDiagFields (nbx_diag_kernels.hpp; checked in nbx_diag.hip)
+// nbx_diag.hip: checks the context's state, then enqueues the diagnostics kernels on its stream; c->diag_dev then holds the
+// kDiagFields raw sums (nbx_diag_kernels.hpp) once the stream gets there
+int enqueue_diagnostics(nbx_ctx* c, const char* where);
+// the raw sums of diag_kernel's field order -> the public struct (kenergy = sum m v^2 / 2, potential = -sum m phi / 2)
+void diag_fill(const double* raw, int32_t i_count, int64_t steps_done, nbx_diag_t* out);
 }  // namespace nbx_detail

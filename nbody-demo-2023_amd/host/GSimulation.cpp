@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/nbx.h"
+#include "../../include/nbx_diag.h"
 #include "cpu_time.hpp"
 #include "rendezvous.hpp"
 #include "snapshot.hpp"
@@ -387,12 +388,28 @@ void GSimulation::start() {
       die_nbx("nbx_upload");
   }
 
+  // NBODY_ENERGY=1: total energy and momentum (include/nbx_diag.h) after upload and after every printed row -- evaluated
+  // outside the timed windows and taken out of the total time, so the table and the rates stay comparable with runs
+  // without it; the drift goes to one `#` line behind the footer and to NBODY_JSON.  Collective in a rank group.
+  const bool energy = env_int("NBODY_ENERGY", 0) != 0;
+  double diag_s = 0.0;  // time spent in the diagnostics inside [t0, t1]
+  auto diagnose = [&](nbx_diag_t* d) {
+    std::memset(d, 0, sizeof(*d));
+    d->struct_size = (int32_t)sizeof(nbx_diag_t);
+    if (grp ? nbx_group_diagnostics(grp, d) : nbx_diagnostics(ctx, d)) die_nbx(grp ? "nbx_group_diagnostics" : "nbx_diagnostics");
+  };
+  nbx_diag_t diag0 = nbx_diag_t(), diag_last = nbx_diag_t();
+  if (energy) {
+    diagnose(&diag0);
+    diag_last = diag0;
+  }
+
   _totTime = 0.;
   const double nd = double(n);
   const double gflops = 1e-9 * ((11. + 18.) * nd * nd + nd * 19.);  // the reference's flop model
   double av = 0.0, dev = 0.0;
   int nf = 0;
-  struct Window { int step; double kenergy, seconds; };
+  struct Window { int step; double kenergy, seconds; nbx_diag_t diag; };
   std::vector<Window> windows;  // for NBODY_JSON: every printed row at full precision
   int retunes = 0;              // windows after which the tuner moved the shares
 
@@ -417,7 +434,14 @@ void GSimulation::start() {
     _kenergy = (real_type)ke;
     nf += 1;
     const double wt = w1 - w0;
-    windows.push_back(Window{done, ke, wt});
+    windows.push_back(Window{done, ke, wt, nbx_diag_t()});
+    if (energy) {
+      CPUTime dtime;
+      const double d0 = dtime.start();
+      diagnose(&diag_last);
+      diag_s += dtime.stop() - d0;
+      windows.back().diag = diag_last;
+    }
     if (weighted && tune) {
       // the reference prints its ratio in front of every row of a tuning run (opencl/Compute.cpp:317-319) and then steps it by 0.01;
       // here the line shows device 0's share of the window just timed, and the next window runs on shares re-weighted by measurement
@@ -440,7 +464,7 @@ void GSimulation::start() {
     }
   }
   const double t1 = time.stop();
-  _totTime = (t1 - t0);
+  _totTime = (t1 - t0) - diag_s;
   _totFlops = gflops * nsteps;
 
   av /= (double)(nf - 2);
@@ -498,6 +522,12 @@ void GSimulation::start() {
     std::cout << "# GPUs / ranks       : " << ranks << " x " << st.i_count << " bodies" << (_multiprocess ? " (one process per rank)" : "")
               << ", position all-gather per step over " << (rccl ? "RCCL" : "device-to-device copies") << std::endl;
   if (!split_note.empty()) std::cout << "# Device word        : " << split_note << std::endl;
+  const double e0 = diag0.kenergy + diag0.potential, e_last = diag_last.kenergy + diag_last.potential;
+  double dp = 0.0;  // |P(last) - P(0)| against the momentum scale sqrt(2 M K(last))
+  if (energy) {
+    for (int k = 0; k < 3; ++k) dp += (diag_last.momentum[k] - diag0.momentum[k]) * (diag_last.momentum[k] - diag0.momentum[k]);
+    dp = std::sqrt(dp) / std::sqrt(2.0 * diag_last.mass * diag_last.kenergy);
+  }
   // NBODY_JSON=<file>: the same facts as one machine-readable line (does not touch stdout)
   if (const char* jp = std::getenv("NBODY_JSON")) {
     if (FILE* jf = std::fopen(jp, "w")) {
@@ -517,10 +547,18 @@ void GSimulation::start() {
                    rccl ? "true" : "false", (int)st.inner_loop, shares_txt.c_str(), (weighted && tune) ? "true" : "false", retunes, split_note.c_str());
       // every printed row: the step, the energy as computed (fp64 sum of the ranks' partials, before the narrowing to
       // real_type that the table shows) and the window's wall time
-      for (size_t k = 0; k < windows.size(); ++k)
-        std::fprintf(jf, "%s{\"step\": %d, \"kenergy\": %.17g, \"seconds\": %.9g}", k ? ", " : "", windows[k].step, windows[k].kenergy,
+      for (size_t k = 0; k < windows.size(); ++k) {
+        std::fprintf(jf, "%s{\"step\": %d, \"kenergy\": %.17g, \"seconds\": %.9g", k ? ", " : "", windows[k].step, windows[k].kenergy,
                      windows[k].seconds);
-      std::fprintf(jf, "]}\n");
+        const nbx_diag_t& d = windows[k].diag;
+        if (energy)
+          std::fprintf(jf, ", \"potential\": %.17g, \"etotal\": %.17g, \"momentum\": [%.17g, %.17g, %.17g]", d.potential, d.kenergy + d.potential,
+                       d.momentum[0], d.momentum[1], d.momentum[2]);
+        std::fprintf(jf, "}");
+      }
+      std::fprintf(jf, "]");
+      if (energy) std::fprintf(jf, ", \"energy_initial\": %.17g", e0);
+      std::fprintf(jf, "}\n");
       std::fclose(jf);
     }
   }
@@ -530,4 +568,7 @@ void GSimulation::start() {
               << 100.0 * 20.0 * pairs_per_s / (st.precision == 32 ? 157.3e12 : 78.6e12)
               << " % of the fp" << st.precision << " vector roofline (20 flop/pair)" << std::endl;
   }
+  if (energy)  // behind the existing `#` lines
+    std::cout << "# Energy             : E(0) = " << std::setprecision(10) << e0 << ", E(" << diag_last.steps_done << ") = " << e_last
+              << ", drift " << std::setprecision(5) << (e_last - e0) / std::fabs(e0) << "; |P - P(0)| / sqrt(2 M K) = " << dp << std::endl;
 }

@@ -28,6 +28,9 @@ SYMBOLS = (
     "nbx_partition_weighted", "nbx_group_create_weighted", "nbx_group_shares", "nbx_tune_weights", "nbx_group_retune",
 )
 
+# the symbols of include/nbx_diag.h (physics diagnostics), kept apart from the set nbx.h declares
+DIAG_SYMBOLS = ("nbx_diagnostics", "nbx_group_diagnostics")
+
 
 class NbxError(RuntimeError):
     def __init__(self, code, where, text):
@@ -60,6 +63,22 @@ class Stats(ctypes.Structure):
     def asdict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
         d["device_name"] = self.device_name.decode(errors="replace")
+        return d
+
+
+class Diag(ctypes.Structure):
+    """nbx_diag_t (include/nbx_diag.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("i_count", ctypes.c_int32), ("steps_done", ctypes.c_int64),
+        ("mass", ctypes.c_double), ("kenergy", ctypes.c_double), ("potential", ctypes.c_double),
+        ("momentum", ctypes.c_double * 3), ("mass_moment", ctypes.c_double * 3),
+    ]
+
+    def asdict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+        d["momentum"] = list(self.momentum)
+        d["mass_moment"] = list(self.mass_moment)
+        d["etotal"] = self.kenergy + self.potential
         return d
 
 
@@ -122,6 +141,8 @@ def load():
     L.nbx_group_shares.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), pd]
     L.nbx_tune_weights.argtypes = [i32, ctypes.POINTER(i32), pd, pd]
     L.nbx_group_retune.argtypes = [vp, pd, ctypes.POINTER(i32)]
+    L.nbx_diagnostics.argtypes = [vp, ctypes.POINTER(Diag)]
+    L.nbx_group_diagnostics.argtypes = [vp, ctypes.POINTER(Diag)]
     _lib = L
     return L
 
@@ -253,6 +274,14 @@ class Context:
         _check(self._L.nbx_stats(self._h, ctypes.byref(s)), "nbx_stats")
         return s.asdict()
 
+    def diagnostics(self):
+        """nbx_diagnostics: this context's owned-slice partials (mass, kenergy, potential, momentum, mass_moment, i_count,
+        steps_done) of the current state, plus etotal = kenergy + potential."""
+        d = Diag()
+        d.struct_size = ctypes.sizeof(Diag)
+        _check(self._L.nbx_diagnostics(self._h, ctypes.byref(d)), "nbx_diagnostics")
+        return d.asdict()
+
 
 class Group:
     """One nbx_group: n_ranks contexts driven by this process (multi-GPU; logical ranks when devices repeat)."""
@@ -302,6 +331,14 @@ class Group:
         ke = ctypes.c_double(0.0)
         _check(self._L.nbx_group_step(self._h, dt, nsteps, ctypes.byref(ke) if kenergy else None), "nbx_group_step")
         return ke.value if kenergy else None
+
+    def diagnostics(self):
+        """nbx_group_diagnostics: system totals summed over the ranks in rank order (collective for rank groups), plus
+        etotal = kenergy + potential."""
+        d = Diag()
+        d.struct_size = ctypes.sizeof(Diag)
+        _check(self._L.nbx_group_diagnostics(self._h, ctypes.byref(d)), "nbx_group_diagnostics")
+        return d.asdict()
 
     def download(self):
         out = {f: np.zeros(self.n, dtype=self.dtype) for f in FIELDS[:6]}

@@ -155,6 +155,10 @@ class NbxEngine:
     def kenergy_partial(self):
         return self.ctx.kenergy_partial()
 
+    def diagnostics_partial(self):
+        """nbx_diagnostics of the owned slice: dict of additive partials (mass, kenergy, potential, momentum, mass_moment)."""
+        return self.ctx.diagnostics()
+
     def download(self):
         return self.ctx.download()
 
@@ -310,6 +314,26 @@ class ShardedSimulation:
             self.dist.all_reduce(t)
             part = float(t.item())
         return 0.5 * part
+
+    DIAG_SCALARS = ("mass", "kenergy", "potential")
+
+    def diagnostics(self):
+        """System mass, kinetic and potential energy, momentum and mass moment of the current state (include/nbx_diag.h),
+        plus etotal = kenergy + potential: the engines' owned-slice partials added by ONE all-reduce of nine doubles."""
+        import torch
+        p = self.engine.diagnostics_partial()
+        vals = [float(p[k]) for k in self.DIAG_SCALARS] + [float(x) for x in p["momentum"]] + [float(x) for x in p["mass_moment"]]
+        if self.dist:
+            t = torch.tensor(vals, dtype=torch.float64)
+            if self.dist.get_backend() == "nccl":
+                t = t.cuda()
+            self.dist.all_reduce(t)
+            vals = [float(x) for x in t.cpu().tolist()]
+        out = dict(zip(self.DIAG_SCALARS, vals[:3]))
+        out["momentum"], out["mass_moment"] = vals[3:6], vals[6:9]
+        out["etotal"] = out["kenergy"] + out["potential"]
+        out["i_count"], out["steps_done"] = self.n, self.steps_done
+        return out
 
     def sync(self):
         self.engine.sync()
