@@ -42,7 +42,7 @@ enum { NBX_LOOP_AUTO = 0, NBX_LOOP_CXX = 1, NBX_LOOP_ASM = 2, NBX_LOOP_ASM_TS = 
 
 /* kernel_variant values */
 enum {
-  NBX_KERNEL_AUTO = 0,  /* chosen by size and summation order (csrc/nbx_api.hip: auto_shape): tree order -- NBX_KERNEL_JLANE below
+  NBX_KERNEL_AUTO = 0,  /* chosen by size and summation order (csrc/nbx_plan.hpp: plan_launch): tree order -- NBX_KERNEL_JLANE below
                            16384 owned bodies (fp64: up to 12288), NBX_KERNEL_SGPRW from there; reference order (fp32 runs of n > 131072) -- NBX_KERNEL_SGPR
                            with one j range and the row epilogue.  nbx_stats reports what was taken */
   NBX_KERNEL_LDS = 1,   /* j-tile (256 records) staged in LDS, broadcast ds_read_b128 (the north-star design) */

@@ -8,19 +8,21 @@
 
 
 #include <algorithm>
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
 #include <new>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "nbx_internal.hpp"
 #include "nbx_kernels.hpp"
 
 using namespace nbx;
-
 using namespace nbx_detail;
 
 namespace nbx_detail {
@@ -33,370 +35,60 @@ std::string& last_error() {
 namespace {
 
 constexpr int kMaxProfiledLaunches = 8192;
-// NBX_ORDER_AUTO: fp32 sums of more terms than this use the reference's order.  131072 x 500 steps agrees with the
-// reference to 2e-5 in tree order (profiles/r01_validate_orders_n131072_s500.log); 262144 x 200 does not (1.3e-3).
-constexpr int kTreeOrderMaxN = 131072;
-// NBX_KERNEL_AUTO, tree order: contexts that own at most this many bodies step with ONE launch (force_jlane_kernel)
-// (12288: 41 us against SGPRW's 48.  Round 3, profiles/r03_band_sweep.txt: between 12288 and 16384 the wave-split kernel falls back
-// to two bodies per lane and, at sizes whose splits are not whole tiles, to the compiled loop -- 40-45 % -- while the one-launch kernel
-// with 8 bodies per wave is 6-15 % ahead: 13000 50.3 vs 53.2 us, 15000 58.0 vs 65.6, 16000 62.8 vs 72.3.)  16384 ITSELF is excluded:
-// there the two tie within 2 %, and SGPRW's summation tree (S = 32) is the one whose chaotic n = 16384 x 500 run -- BASELINE
-// configs[1] -- stays inside the 1e-4 gate at every printed step (profiles/r02_config1_by_kernel.txt, r03_config1_by_shape.txt).
-constexpr int kJlaneMaxOwn = 16383;
-// Tree order, wave-split kernel: contexts that own up to this many bodies keep round 1's split rule (S = 32 at 16384).  Fewer
-// splits are 5 % faster there (profiles/r03_band_sweep.txt: S = 4 or 8), but BASELINE.json configs[1] -- n = 16384 x 500 steps, 450 of
-// them after the bounce -- is decided at the reference's own noise level, and of S = 2, 4, 8, 16, 32 only the tree of S = 32
-// lands inside 1e-4 at every printed row (7.7e-5; the others 1.05e-4 ... 1.43e-4, two builds of the reference itself 1.3e-4:
-// profiles/r03_config1_by_shape.txt).  tests/test_parity_gpu.py::test_config1_launch_shape_is_frozen pins it.
-constexpr int kRound1SplitMaxOwn = 16384;
-constexpr int kJlaneMaxOwnF64 = 12288;  // fp64 form: 92 us against 97 at 12288, SGPRW ahead at 16384 (profiles/r02_jlane_f64_ab.txt)
-
-}  // namespace
-
-namespace {
 
 // ------------------------------------------------------------------------------------------
-// kernel dispatch
+// kernel dispatch: one launcher per entry of kInstances (nbx_plan.hpp) -- the only kernel instances this library compiles
 // ------------------------------------------------------------------------------------------
-template <typename T, int B, int JSRC, int EPI, int MATH, bool WS, int LOOP = LOOP_CXX>
-void launch_force_t(const ForceArgs<T>& a, dim3 grid, hipStream_t st) {
-  hipLaunchKernelGGL((force_kernel<T, B, JSRC, EPI, 1, MATH, WS, LOOP>), grid, dim3(kBlock), 0, st, a);
-}
-
-// does a hand-scheduled (LOOP_ASM) instance exist for this combination?
-template <typename T, int JSRC, int EPI, int MATH, bool WS>
-constexpr bool kHasAsmLoop = sizeof(T) == 4 && JSRC == JSRC_SGPR && MATH == MATH_PACKED;
+static_assert(kSgprGran == (kSgprAsmTrip<1> > 64 ? kSgprAsmTrip<1> : 64) && kSgprGran % kSgprAsmTrip<2> == 0 &&
+                  kSgprGran % kSgprAsmTrip<4> == 0 && kTile % kSgprGran == 0,
+              "j ranges are whole trips of the asm loop");
 
 template <typename T>
-using ForceLauncher = void (*)(const ForceArgs<T>&, dim3, hipStream_t);
-
-template <typename T, int JSRC, int EPI, int MATH, bool WS>
-ForceLauncher<T> pick_b(int B, int loop) {
-  if constexpr (sizeof(T) == 4 && JSRC == JSRC_SGPR && MATH == MATH_SCALAR && !WS) {
-    // one body per lane: the hand-scheduled loop is the two-j-records-per-operation one (sgpr_loop_asm_jpair)
-    if (B == 1 && loop != LOOP_CXX) return launch_force_t<T, 1, JSRC, EPI, MATH, WS, LOOP_ASM>;
-  }
-  if constexpr (kHasAsmLoop<T, JSRC, EPI, MATH, WS>) {
-    if constexpr (!WS && EPI == EPI_ROW) {  // time-sliced priority: the whole-launch-resident reference-order shapes only
-      if (loop == LOOP_ASM_TS) {
-        if (B == 2) return launch_force_t<T, 2, JSRC, EPI, MATH, WS, LOOP_ASM_TS>;
-        if (B == 4) return launch_force_t<T, 4, JSRC, EPI, MATH, WS, LOOP_ASM_TS>;
-        return nullptr;
-      }
-      if (loop == LOOP_ASM_PF) {  // L2 prefetch: same scope (one workgroup row, one wave per SIMD)
-        if (B == 2) return launch_force_t<T, 2, JSRC, EPI, MATH, WS, LOOP_ASM_PF>;
-        if (B == 4) return launch_force_t<T, 4, JSRC, EPI, MATH, WS, LOOP_ASM_PF>;
-        return nullptr;
-      }
-    }
-    if (loop == LOOP_ASM_TS || loop == LOOP_ASM_PF) loop = LOOP_ASM;  // e.g. nbx_accel's slab form of a time-sliced context
-    if (loop == LOOP_ASM) {
-      if (B == 2) return launch_force_t<T, 2, JSRC, EPI, MATH, WS, LOOP_ASM>;
-      if (B == 4) return launch_force_t<T, 4, JSRC, EPI, MATH, WS, LOOP_ASM>;
-      return nullptr;
-    }
-  } else if (loop != LOOP_CXX) {
-    return nullptr;
-  }
-  switch (B) {
-    case 1:
-      if constexpr (MATH == MATH_SCALAR) return launch_force_t<T, 1, JSRC, EPI, MATH, WS>;
-      return nullptr;
-    // fp32 runs B >= 2 on the packed pipe only: the scalar-math B >= 2 instances are not built
-    case 2:
-      if constexpr (sizeof(T) == 8 || MATH == MATH_PACKED) return launch_force_t<T, 2, JSRC, EPI, MATH, WS>;
-      return nullptr;
-    case 4:
-      if constexpr (sizeof(T) == 8 || MATH == MATH_PACKED) return launch_force_t<T, 4, JSRC, EPI, MATH, WS>;
-      return nullptr;
-    case 8:
-      if constexpr (sizeof(T) == 4 && !WS && MATH == MATH_PACKED) return launch_force_t<T, 8, JSRC, EPI, MATH, WS>;
-      return nullptr;
-  }
-  return nullptr;
-}
-
-template <typename T, int JSRC, int MATH, bool WS>
-ForceLauncher<T> pick_epi(int B, int epi, int loop) {
-  if (epi == EPI_ROW) {
-    if constexpr (!WS) return pick_b<T, JSRC, EPI_ROW, MATH, WS>(B, loop);
-    return nullptr;
-  }
-  return pick_b<T, JSRC, EPI_SLAB, MATH, WS>(B, loop);
-}
-
-template <typename T, int MATH>
-ForceLauncher<T> pick(int B, int variant, int epi, int loop) {
-  if (variant == NBX_KERNEL_SGPRW) return pick_epi<T, JSRC_SGPR, MATH, true>(B, epi, loop);
-  if (variant == NBX_KERNEL_SGPR) return pick_epi<T, JSRC_SGPR, MATH, false>(B, epi, loop);
-  return pick_epi<T, JSRC_LDS, MATH, false>(B, epi, loop);
-}
-
-// One body per lane on the plain SGPR kernel: its hand-scheduled loop packs two consecutive j records per operation and reads the
-// pair-interleaved copy of the records (nbx_ctx::posm_pairs)
-bool jpair_shape(const nbx_ctx* c) {
-  return c->precision == 32 && c->variant == NBX_KERNEL_SGPR && c->math == MATH_SCALAR && c->B == 1 && c->jps % kSgprAsmTrip<1> == 0;
-}
-
-// Does the hand-scheduled loop exist for this shape?  (mirror of kHasAsmLoop for run-time shape decisions)
-bool asm_loop_available(const nbx_ctx* c, int epi) {
-  (void)epi;
-  if (c->variant == NBX_KERNEL_JLANE) return c->precision == 32 && (c->B == 2 || c->B == 4 || c->B == 8);
-  if (c->variant == NBX_KERNEL_SGPRW && c->jps % 256 != 0) return false;  // a wave walks a quarter of a split: whole trips only
-  if (jpair_shape(c)) return true;
-  return c->precision == 32 && (c->variant == NBX_KERNEL_SGPR || c->variant == NBX_KERNEL_SGPRW) && c->math == MATH_PACKED && (c->B == 2 || c->B == 4);
-}
-
-template <typename T>
-ForceLauncher<T> pick_force(const nbx_ctx* c, int epi) {
-  // nbx_accel runs the EPI_SLAB form of a context whose step kernel may be another epilogue: decide per call
-  const int loop = (c->loop != LOOP_CXX && asm_loop_available(c, epi)) ? c->loop : LOOP_CXX;
-  if constexpr (sizeof(T) == 4) {
-    if (c->math == MATH_PACKED) return pick<float, MATH_PACKED>(c->B, c->variant, epi, loop);
-  }
-  return pick<T, MATH_SCALAR>(c->B, c->variant, epi, loop);
-}
-
-
-// Bodies per lane of the reference-order kernel (one chain per owned body, S = 1).  Its run time is quantised: the
-// ceil(own / (256 B)) workgroups are spread over the CUs, and a launch takes as long as the fullest CU, which holds
-// r = ceil(workgroups / CUs) of them.  Measured on MI355X at n = 1048576 with the hand-scheduled loop for B = 2 and 4
-// (profiles/r02_reference_order_thresholds.txt), ms for r = 1, 2, 3, ...: B = 1, compiled loop: 31.0, 48.6, 70.3, 91, 112 (plain VALU ops);
-// B = 2: 31.5 (30.0 with the L2 prefetch and the 256-record trips of LOOP_ASM_PF, round 4), 59.6, 88.5, 118;  B = 4: 59.3, 117.4, 175.6, 234.6 -- linear in r after
-// the first workgroup.  With two workgroups on the fullest CU the time-sliced loop applies (LOOP_ASM_TS): B = 2, r = 2 then costs 58.0
-// (profiles/r02_time_sliced_ab.txt: 57.98 ms for 262144 of 1M bodies), B = 4, r = 2 117.0.  Round 4: one body per lane with the
-// two-j-records-per-operation loop (sgpr_loop_asm_jpair, `jpair`): 17.9 for r = 1 (65536 of 1M bodies: 48.8 % of the roofline against 28.4 %
-// for the compiled loop and 27.8 % for B = 2 on half the CUs), 34.3 for r = 2 (profiles/r04_jpair_ab.txt) -- so it takes every slice of up to
-// 256 x CUs = 65536 bodies, and B = 2 keeps 65537 ... 131072.  Pick the B with the smallest estimate; ties go to the larger B (fewer
-// workgroups stream the j records).  Only the ratios matter, so the table serves every n.
-int reference_order_bodies_per_lane(int own, int cus, int max_b, bool jpair, double* cost_out = nullptr) {
-  struct Cost { int b; double first, next, two; };
-  static const Cost kCost[] = {{1, 31.0, 20.2, 0.0}, {2, 30.0, 29.25, 58.0}, {4, 59.8, 58.2, 117.0}};
-  static const Cost kJpair = {1, 17.9, 16.4, 0.0};  // one body per lane, two j records per packed operation
-  int best = 1;
-  double best_t = 0.0;
-  for (const auto& k0 : kCost) {
-    const auto& k = (k0.b == 1 && jpair) ? kJpair : k0;
-    if (k.b > max_b) continue;
-    const int wgs = ceil_div(own, kBlock * k.b);
-    const int r = std::max(1, ceil_div(wgs, std::max(1, cus)));
-    const double t = (r == 2 && k.two > 0.0) ? k.two : k.first + k.next * (r - 1);
-    if (best_t == 0.0 || t <= best_t * 1.01) { best = k.b; best_t = std::min(t, best_t == 0.0 ? t : best_t); }
-  }
-  // Where two bodies per lane load every CU evenly too (twice the workgroups, all CUs with the same count), they win over four
-  // by 2.5 % at 262144 owned bodies and tie from 524288 up (the younger wave of a SIMD fills the older one's issue bubbles;
-  // profiles/r02_loop_ab_asm_vs_cxx.txt, same process on two boxes): take them.
-  if (best == 4 && max_b >= 2 && ceil_div(own, kBlock * 2) % std::max(1, cus) == 0) best = 2;
-  if (cost_out) *cost_out = best_t;
-  return best;
-}
-
-// j-splits of the wave-split kernel with the hand-scheduled loop (round 3, profiles/r03_band_sweep.txt).  Round 1's rule -- 32
-// workgroups per CU, i.e. S = 32 up to n = 65536 -- suited the compiler-scheduled loop, which needed eight waves per SIMD to
-// hide its own bubbles.  The hand-scheduled loop is at its rate with two, and every extra split costs a slab write, a slab
-// read by integrate_kernel and a shorter j loop per wave.  The launch lasts as long as the fullest CU: ceil(bi S / CUs)
-// workgroups of 1/S of the j range each.  Take the S (power of two) that minimises that product; among equals the smallest
-// S that still gives every CU two workgroups.  Measured optimum at every size tried: 24576 -> 8 (+2.6 % over S = 32),
-// 32768 -> 4 (+1.9 %), 49152 -> 4 (+1.2 %), 65536 -> 2 (+1.2 %); three workgroups on half the CUs (24576 with S = 4) is 20 % slower.
-int balanced_j_split(int bi, int cus, int max_s) {
-  double best_cost = 0.0;
-  for (int S = 1; S <= max_s; S *= 2) {
-    const double cost = (double)ceil_div(bi * S, cus) / S;
-    if (best_cost == 0.0 || cost < best_cost) best_cost = cost;
-  }
-  int pick = 0, largest = 1;
-  for (int S = 1; S <= max_s; S *= 2) {
-    if ((double)ceil_div(bi * S, cus) / S > best_cost * 1.0001) continue;
-    largest = S;
-    if (!pick && bi * S >= 2 * cus) pick = S;
-  }
-  return pick ? pick : largest;
-}
-
-// Launch shape.  Measured with tools/kbench on MI355X (profiles/r01_kbench_*): the force kernel is
-// VALU-issue bound and wants all 8 wave slots of every SIMD filled, i.e. >= 8192 workgroups of 256
-// threads (32 per CU).  Fastest shape from n = 2k to 1M: j records in SGPRs, the four waves of a
-// workgroup sharing 64*B bodies and splitting the j range (NBX_KERNEL_SGPRW), B = 4 bodies per lane
-// (two packed register pairs; B = 2 for short i ranges), plus S j-range splits across workgroups:
-// 58-60 % of the fp32 roofline at n >= 64k, 52 % at 16k, vs 52 % / 36 % for B = 8 / LDS tile.
-void auto_shape(nbx_ctx* c, const nbx_opts& o) {
-  const int cus = c->prop.multiProcessorCount > 0 ? c->prop.multiProcessorCount : 256;
-  const int target_wgs = cus * 32;
-  int variant = o.kernel_variant;
-  if (variant == NBX_KERNEL_EXACT || variant == NBX_KERNEL_EXACT_FMA) {  // one thread per body, no blocking, no splits, separate integrate kernel
-    c->B = 1; c->S = 1; c->jps = c->n_alloc; c->math = MATH_SCALAR; c->variant = variant; c->epi = EPI_SLAB;
-    c->order = NBX_ORDER_REFERENCE;  // one accumulator per body, j ascending: it IS the reference's loop
-    c->grid = dim3(ceil_div(c->i_count, kBlock), 1);
-    return;
-  }
-  // Summation order (include/nbx.h).  The reference adds a body's n terms one after the other into one fp32
-  // accumulator; from n = 262144 that sum carries ~1e-5 of rounding noise per step which heats the system (kenergy
-  // +5e-4..1e-3 against an fp64 run; 1.6e-5 over 500 steps at n = 131072).  A tree of partial sums does not reproduce
-  // that, a single accumulator per body in the same j order does (to 5e-5 / 5e-7, tools/validate_big.py) -- at the
-  // price of one chain per owned body.  The noise is a property of the LENGTH of the sum, i.e. of n, not of how many
-  // bodies this context owns: every rank of a sharded run takes the same decision.
-  int order = o.summation_order;
-  if (order != NBX_ORDER_REFERENCE && order != NBX_ORDER_TREE) {
-    const bool shape_given = o.j_split > 0 || variant == NBX_KERNEL_SGPRW || variant == NBX_KERNEL_JLANE;  // tree-only shapes
-    if (o.j_split == 1 && variant != NBX_KERNEL_SGPRW) order = NBX_ORDER_REFERENCE;
-    // fp64 keeps the tree: its summation noise (~1e-13) is far below the 1e-10 fp64 gate in either order
-    else order = (!shape_given && c->precision == 32 && c->n > kTreeOrderMaxN) ? NBX_ORDER_REFERENCE : NBX_ORDER_TREE;
-  }
-  c->order = order;
-  if (order == NBX_ORDER_REFERENCE) {
-    if (variant != NBX_KERNEL_LDS && variant != NBX_KERNEL_SGPR) variant = NBX_KERNEL_SGPR;
-    int B = o.bodies_per_lane;
-    const int maxBr = c->precision == 32 ? 8 : 4;
-    if (B != 1 && B != 2 && B != 4 && B != 8) B = 0;
-    if (B > maxBr) B = maxBr;
-    // fp32, plain SGPR kernel, hand-scheduled loops allowed: one body per lane means sgpr_loop_asm_jpair
-    const bool jpair = c->precision == 32 && variant == NBX_KERNEL_SGPR && o.inner_loop != NBX_LOOP_CXX;
-    if (B == 0) B = reference_order_bodies_per_lane(c->i_count, cus, maxBr, jpair);
-    c->B = B; c->S = 1; c->jps = c->n_alloc; c->variant = variant;
-    c->math = (c->precision == 32 && B >= 2) ? MATH_PACKED : MATH_SCALAR;
-    c->epi = o.fused_epilogue == 2 ? EPI_SLAB : EPI_ROW;
-    c->grid = dim3(ceil_div(c->i_count, kBlock * B), 1);
-    return;
-  }
-  // Launch-bound sizes (fp32): one launch per step with the lanes of a wave splitting j (force_jlane_kernel).  Bodies per
-  // wave: the power of two that gives about one wave per SIMD (1024 waves), between 2 and 16.
-  const int max_nb = c->precision == 32 ? 16 : 8;  // fp64 bodies take two SGPRs per coordinate
-  const bool jlane_auto = variant == NBX_KERNEL_AUTO && o.j_split <= 0 && o.bodies_per_lane == 0 && o.fused_epilogue != 2 &&
-                          c->i_count <= (c->precision == 32 ? kJlaneMaxOwn : kJlaneMaxOwnF64);
-  if (variant == NBX_KERNEL_JLANE || jlane_auto) {
-    int NB = o.bodies_per_lane;
-    if ((NB != 2 && NB != 4 && NB != 8 && NB != 16) || NB > max_nb) {
-      // A launch lasts as long as the fullest SIMD: ceil(waves / SIMDs) rounds of NB bodies each, times what a body-round costs
-      // with that NB.  Measured per body-round and per j record, relative to NB = 8 (profiles/r03_jlane_band.txt: the same ratios
-      // at 12288, 13000 and 16383 bodies): 2 bodies per wave 1.29 (every wave streams all j records and transposes through LDS
-      // for two bodies only), 4 -> 1.06, 8 -> 1.00 (the generated loop), 16 -> 1.06 (compiled loop only).  Smallest product wins:
-      // 2048 -> 2, 4096 -> 4, 8192 -> 8, 12288 -> 4 (three full rounds), 13000 ... 16383 -> 8 -- the measured optimum at each.
-      // Round 2 counted body-rounds alone, which sent 13000 and 14336 to NB = 2 (56.6 us against 50.1 with 8).
-      // fp64 (no generated loop, other ratios not measured): body-rounds alone, ties to the larger NB, as in round 2.
-      long best = 0;
-      for (int nb = 2; nb <= max_nb; nb *= 2) {
-        const long weight = c->precision != 32 ? 100 : (nb == 2 ? 129 : nb == 8 ? 100 : 106);
-        const long cost = (long)ceil_div(ceil_div(c->i_count, nb), cus * 4) * nb * weight;
-        if (best == 0 || cost <= best) { best = cost; NB = nb; }
-      }
-    }
-    c->B = NB; c->S = 1; c->jps = c->n_alloc; c->math = c->precision == 32 ? MATH_PACKED : MATH_SCALAR; c->variant = NBX_KERNEL_JLANE; c->epi = EPI_ROW;
-    c->grid = dim3(ceil_div(ceil_div(c->i_count, NB), 4), 1);
-    return;
-  }
-  if (variant != NBX_KERNEL_LDS && variant != NBX_KERNEL_SGPR && variant != NBX_KERNEL_SGPRW) variant = NBX_KERNEL_SGPRW;
-  const int maxB = (c->precision == 32 && variant != NBX_KERNEL_SGPRW) ? 8 : 4;
-  int B = o.bodies_per_lane;
-  if (B != 1 && B != 2 && B != 4 && B != 8) B = 0;
-  if (B > maxB) B = maxB;
-  if (B == 0) B = c->i_count >= 16384 ? 4 : 2;
-  const int iblk = (variant == NBX_KERNEL_SGPRW ? 64 : kBlock) * B;  // bodies per workgroup
-  // j-range granularity of one split: a whole LDS tile / two pipelined SGPR batches (per wave)
-  // (the hand-scheduled loop of the plain SGPR kernel walks whole trips of up to 64 records)
-  // (round 3: where the balanced split rule applies -- few, long splits -- a split is a whole number of 256-record tiles, so
-  // that every wave's quarter is whole trips of the hand-scheduled loop whatever n is: n = 50000 used to get 32 splits of 1568
-  // records and, with them, the compiler-scheduled loop)
-  // Only where tree order is what AUTO takes (n <= 131072).  Above that it runs on request alone -- asked for because it is closer to the
-  // true sum than the reference's single chain -- and the number of chains is what buys that: n = 262144 keeps its 8 x 4, 1M its 2 x 4.
-  const bool balanced = o.j_split <= 0 && c->precision == 32 && variant == NBX_KERNEL_SGPRW && c->i_count > kRound1SplitMaxOwn && c->n <= kTreeOrderMaxN;
-  constexpr int kSgprGran = kSgprAsmTrip<1> > 64 ? kSgprAsmTrip<1> : 64;  // whole trips of every hand-scheduled loop of the plain SGPR kernel
-  const int gran = variant == NBX_KERNEL_LDS ? kTile : (variant == NBX_KERNEL_SGPR ? kSgprGran : (balanced ? 256 : 32));
-  static_assert(kSgprGran % kSgprAsmTrip<2> == 0 && kSgprGran % kSgprAsmTrip<4> == 0 && kSgprGran % kSgprAsmTrip<1> == 0 && kTile % kSgprGran == 0,
-                "j ranges are whole trips of the asm loop");
-  const int max_split = std::max(1, c->n_alloc / gran);
-  int S = o.j_split;
-  if (S <= 0) {
-    const int bi = ceil_div(c->i_count, iblk);
-    if (balanced) S = balanced_j_split(bi, cus, std::min(32, max_split));
-    else S = std::min(32, ceil_div(target_wgs, bi));
-    // the S partial-acceleration slabs are written and re-read every step: keep them <= 256 MiB
-    while (S > 1 && (size_t)S * c->own_pad * c->rec > ((size_t)256 << 20)) S /= 2;
-  }
-  S = std::max(1, std::min(S, max_split));
-  int jps = round_up(ceil_div(c->n_alloc, S), gran);
-  S = ceil_div(c->n_alloc, jps);  // drop empty tail splits
-  c->B = B;
-  c->S = S;
-  c->jps = jps;
-  c->math = (c->precision == 32 && B >= 2) ? MATH_PACKED : MATH_SCALAR;
-  c->variant = variant;
-  // fused_epilogue: 0 auto, 1 on, 2 off.  A single split integrates directly (EPI_ROW); shapes with j-splits always
-  // use the separate integrate kernel (one launch per step for small n is NBX_KERNEL_JLANE's job).
-  if (o.fused_epilogue == 2) c->epi = EPI_SLAB;
-  else if (S == 1 && variant != NBX_KERNEL_SGPRW) c->epi = EPI_ROW;
-  else c->epi = EPI_SLAB;
-  c->grid = dim3(ceil_div(c->i_count, iblk), S);
-}
-
-template <typename T>
-int enqueue_force(nbx_ctx* c, int epi, double dt) {
-  if (c->variant == NBX_KERNEL_EXACT || c->variant == NBX_KERNEL_EXACT_FMA) {
-    using T4 = typename V4<T>::type;
-    if (c->variant == NBX_KERNEL_EXACT)
-      hipLaunchKernelGGL((force_exact_kernel<T, false>), c->grid, dim3(kBlock), 0, c->stream, (const T4*)c->posm[c->cur],
-                         (const T*)c->mass_all, (T4*)c->accp, c->i_begin, c->i_count, c->n);
-    else
-      hipLaunchKernelGGL((force_exact_kernel<T, true>), c->grid, dim3(kBlock), 0, c->stream, (const T4*)c->posm[c->cur],
-                         (const T*)c->mass_all, (T4*)c->accp, c->i_begin, c->i_count, c->n);
-    HIP_TRY(hipGetLastError());
-    return NBX_OK;
-  }
-  ForceLauncher<T> fn = c->variant == NBX_KERNEL_JLANE ? nullptr : pick_force<T>(c, epi);
-  if (!fn && c->variant != NBX_KERNEL_JLANE) return fail(NBX_ERR_ARG, "no kernel instance for this bodies_per_lane / precision");
-  ForceArgs<T> a{};
+ForceArgs<T> force_args(const nbx_ctx* c, double dt) {
   using T4 = typename V4<T>::type;
-  a.posm = (const T4*)c->posm[c->cur];
-  a.accp = (T4*)c->accp;
-  a.velm = (T4*)c->velm;
-  a.posm_next = (T4*)c->posm[c->cur ^ 1];
-  a.ke_part = c->ke_part;
-  a.i_begin = c->i_begin;
-  a.i_count = c->i_count;
-  a.own_pad = c->own_pad;
-  a.j_per_split = c->jps;
-  a.n_alloc = c->n_alloc;
-  a.dt = (T)dt;
-  a.slice_bit = c->slice_bit;
-  a.posm_pairs = (const T4*)c->posm_pairs;
-  if constexpr (sizeof(T) == 4) {
-    if (c->loop == LOOP_ASM && jpair_shape(c)) {  // this step's pair-interleaved copy of the records (all n_alloc of them: other ranks' blocks arrived by all-gather)
-      const int npairs = c->n_alloc / 2;
-      hipLaunchKernelGGL(pair_transpose_kernel, dim3(ceil_div(npairs, kBlock)), dim3(kBlock), 0, c->stream, (const float4*)c->posm[c->cur],
-                         (float4*)c->posm_pairs, npairs);
-    }
+  ForceArgs<T> a{};
+  a.posm = (const T4*)c->posm[c->cur]; a.posm_next = (T4*)c->posm[c->cur ^ 1]; a.posm_pairs = (const T4*)c->posm_pairs;
+  a.accp = (T4*)c->accp; a.velm = (T4*)c->velm; a.ke_part = c->ke_part;
+  a.i_begin = c->i_begin; a.i_count = c->i_count; a.own_pad = c->own_pad; a.j_per_split = c->plan.jps; a.n_alloc = c->n_alloc;
+  a.dt = (T)dt; a.slice_bit = c->slice_bit;
+  return a;
+}
+
+// acc_only: the jlane kernels store the accelerations instead of integrating (nbx_accel)
+template <int I>
+void launch_instance(nbx_ctx* c, double dt, int acc_only) {
+  constexpr Instance k = kInstances[I];
+  using T = std::conditional_t<k.precision == 32, float, double>;
+  using T4 = typename V4<T>::type;
+  const dim3 grid(c->plan.grid_x, c->plan.grid_y);
+  if constexpr (k.kind == INST_EXACT)
+    hipLaunchKernelGGL((force_exact_kernel<T, k.B == 1>), grid, dim3(kBlock), 0, c->stream, (const T4*)c->posm[c->cur],
+                       (const T*)c->mass_all, (T4*)c->accp, c->i_begin, c->i_count, c->n);
+  else if constexpr (k.kind == INST_FORCE)
+    hipLaunchKernelGGL((force_kernel<T, k.B, k.jsrc, k.epi, 1, k.math, k.ws, k.loop>), grid, dim3(kBlock), 0, c->stream, force_args<T>(c, dt));
+  else if constexpr (k.precision == 32)  // D = prefetch depth of the compiled loop / tail; the generated loop exists for NB <= 8
+    hipLaunchKernelGGL((force_jlane_kernel<k.B, (k.B <= 4 ? 8 : 4), k.loop>), grid, dim3(kBlock), 0, c->stream, force_args<T>(c, dt), acc_only);
+  else
+    hipLaunchKernelGGL((force_jlane_kernel_f64<k.B, (k.B == 2 ? 8 : 4)>), grid, dim3(kBlock), 0, c->stream, force_args<T>(c, dt), acc_only);
+}
+
+template <int... I>
+constexpr std::array<void (*)(nbx_ctx*, double, int), sizeof...(I)> make_launchers(std::integer_sequence<int, I...>) {
+  return {{&launch_instance<I>...}};
+}
+constexpr auto kLaunchers = make_launchers(std::make_integer_sequence<int, kInstanceCount>{});
+
+// the step kernel, or (accel) nbx_accel's slab form of it
+int enqueue_force(nbx_ctx* c, bool accel, double dt) {
+  if (c->plan.pairs) {  // this step's pair-interleaved copy of the records (all n_alloc of them: other ranks' blocks arrived by all-gather)
+    const int npairs = c->n_alloc / 2;
+    hipLaunchKernelGGL(pair_transpose_kernel, dim3(ceil_div(npairs, kBlock)), dim3(kBlock), 0, c->stream, (const float4*)c->posm[c->cur],
+                       (float4*)c->posm_pairs, npairs);
   }
-  const bool prof = c->profiling && c->ev_used + 2 <= c->ev.size();
+  // the exact kernel (validation) is not timed
+  const bool prof = c->profiling && c->plan.step.kind != INST_EXACT && c->ev_used + 2 <= c->ev.size();
   if (prof) HIP_TRY(hipEventRecord(c->ev[c->ev_used], c->stream));
-  if (c->variant == NBX_KERNEL_JLANE) {
-    if constexpr (sizeof(T) == 4) {
-      const int acc_only = epi == EPI_SLAB ? 1 : 0;  // nbx_accel asks for the slab form: accelerations only
-      const bool hand = c->loop == LOOP_ASM;  // the generated main loop (NB <= 8); D = prefetch depth of the compiled loop / tail
-      switch (c->B) {
-        case 2:
-          if (hand) hipLaunchKernelGGL((force_jlane_kernel<2, 8, LOOP_ASM>), c->grid, dim3(kBlock), 0, c->stream, a, acc_only);
-          else hipLaunchKernelGGL((force_jlane_kernel<2, 8>), c->grid, dim3(kBlock), 0, c->stream, a, acc_only);
-          break;
-        case 4:
-          if (hand) hipLaunchKernelGGL((force_jlane_kernel<4, 8, LOOP_ASM>), c->grid, dim3(kBlock), 0, c->stream, a, acc_only);
-          else hipLaunchKernelGGL((force_jlane_kernel<4, 8>), c->grid, dim3(kBlock), 0, c->stream, a, acc_only);
-          break;
-        case 8:
-          if (hand) hipLaunchKernelGGL((force_jlane_kernel<8, 4, LOOP_ASM>), c->grid, dim3(kBlock), 0, c->stream, a, acc_only);
-          else hipLaunchKernelGGL((force_jlane_kernel<8, 4>), c->grid, dim3(kBlock), 0, c->stream, a, acc_only);
-          break;
-        default: hipLaunchKernelGGL((force_jlane_kernel<16, 4>), c->grid, dim3(kBlock), 0, c->stream, a, acc_only); break;
-      }
-    } else {
-      const int acc_only = epi == EPI_SLAB ? 1 : 0;
-      switch (c->B) {
-        case 2: hipLaunchKernelGGL((force_jlane_kernel_f64<2, 8>), c->grid, dim3(kBlock), 0, c->stream, a, acc_only); break;
-        case 4: hipLaunchKernelGGL((force_jlane_kernel_f64<4, 4>), c->grid, dim3(kBlock), 0, c->stream, a, acc_only); break;
-        default: hipLaunchKernelGGL((force_jlane_kernel_f64<8, 4>), c->grid, dim3(kBlock), 0, c->stream, a, acc_only); break;
-      }
-    }
-  } else {
-    fn(a, c->grid, c->stream);
-  }
+  (accel ? c->launch_accel : c->launch_step)(c, dt, accel ? 1 : 0);
   if (prof) {
     HIP_TRY(hipEventRecord(c->ev[c->ev_used + 1], c->stream));
     c->ev_used += 2;
@@ -406,21 +98,21 @@ int enqueue_force(nbx_ctx* c, int epi, double dt) {
 }
 
 // energy partials one step of this context's shape writes: one per workgroup of the kernel that integrates
-int step_ke_parts(const nbx_ctx* c) { return c->epi != EPI_SLAB ? (int)c->grid.x : ceil_div(c->i_count, kBlock); }
+int step_ke_parts(const nbx_ctx* c) { return c->plan.epi != EPI_SLAB ? c->plan.grid_x : ceil_div(c->i_count, kBlock); }
 
 // one local step: force (+ integrate) into the next buffer; does not swap
 template <typename T>
 int enqueue_step(nbx_ctx* c, double dt) {
   using T4 = typename V4<T>::type;
-  int rc = enqueue_force<T>(c, c->epi, dt);
+  int rc = enqueue_force(c, false, dt);
   if (rc) return rc;
-  if (c->epi != EPI_SLAB) {
+  if (c->plan.epi != EPI_SLAB) {
     c->ke_parts = step_ke_parts(c);
   } else {
     const int blocks = step_ke_parts(c);
     hipLaunchKernelGGL((integrate_kernel<T>), dim3(blocks), dim3(kBlock), 0, c->stream,
                        (const T4*)c->posm[c->cur], (T4*)c->posm[c->cur ^ 1], (T4*)c->velm,
-                       (const T4*)c->accp, c->S, c->own_pad, c->i_begin, c->i_count, (T)dt, c->ke_part);
+                       (const T4*)c->accp, c->plan.S, c->own_pad, c->i_begin, c->i_count, (T)dt, c->ke_part);
     HIP_TRY(hipGetLastError());
     c->ke_parts = blocks;
   }
@@ -489,19 +181,8 @@ int drain_profile(nbx_ctx* c) {
 }
 
 }  // namespace
-// What one force launch of this context would cost, in relative units, if the context owned `own` bodies instead: the cost table of
-// reference_order_bodies_per_lane in reference order (a step function of `own`: the launch lasts as long as its fullest CU), and `own`
-// itself in tree order, where j-splits keep the time close to proportional.  The tuner of nbx_group_retune uses the RATIO of two such
-// values to predict what a move of the shares would do before it makes it.
-double nbx_detail::model_force_cost(const nbx_ctx* c, int own) {
-  if (own <= 0) return 0.0;
-  if (c->order != NBX_ORDER_REFERENCE) return (double)own;
-  const int cus = c->prop.multiProcessorCount > 0 ? c->prop.multiProcessorCount : 256;
-  const bool jpair = c->precision == 32 && c->variant == NBX_KERNEL_SGPR;
-  double t = 0.0;
-  (void)reference_order_bodies_per_lane(own, cus, c->precision == 32 ? 8 : 4, jpair, &t);
-  return t;
-}
+// the tuner's predictor: nbx_plan.hpp, force_cost
+double nbx_detail::model_force_cost(const nbx_ctx* c, int own) { return force_cost(c->plan, c->precision, c->prop.multiProcessorCount, own); }
 
 int nbx_detail::use_device(nbx_ctx* c) {
   HIP_TRY(hipSetDevice(c->device));
@@ -564,14 +245,14 @@ int download_t(nbx_ctx* c, T* px, T* py, T* pz, T* vx, T* vy, T* vz) {
 template <typename T>
 int accel_t(nbx_ctx* c, T* ax, T* ay, T* az) {
   using T4 = typename V4<T>::type;
-  int rc = enqueue_force<T>(c, EPI_SLAB, 0.0);
+  int rc = enqueue_force(c, true, 0.0);
   if (rc) return rc;
-  std::vector<T4> h((size_t)c->S * c->own_pad);
+  std::vector<T4> h((size_t)c->plan.S * c->own_pad);
   HIP_TRY(hipMemcpyAsync(h.data(), c->accp, sizeof(T4) * h.size(), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (int k = 0; k < c->i_count; ++k) {
     T sx = (T)0, sy = (T)0, sz = (T)0;
-    for (int s = 0; s < c->S; ++s) {  // same order as integrate_kernel
+    for (int s = 0; s < c->plan.S; ++s) {  // same order as integrate_kernel
       const T4& q = h[(size_t)s * c->own_pad + k];
       sx += q.x; sy += q.y; sz += q.z;
     }
@@ -646,49 +327,17 @@ int nbx_create(nbx_ctx** out, int32_t n, int32_t precision, const nbx_opts* opts
     CREATE_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     c->own_stream = true;
   }
-  auto_shape(c, o);
-  if (o.inner_loop != NBX_LOOP_AUTO && o.inner_loop != NBX_LOOP_CXX && o.inner_loop != NBX_LOOP_ASM && o.inner_loop != NBX_LOOP_ASM_TS &&
-      o.inner_loop != NBX_LOOP_ASM_PF)
-    return fail(NBX_ERR_ARG, "nbx_create: inner_loop must be NBX_LOOP_AUTO, NBX_LOOP_CXX, NBX_LOOP_ASM, NBX_LOOP_ASM_TS or NBX_LOOP_ASM_PF");
-  c->loop = (o.inner_loop != NBX_LOOP_CXX && asm_loop_available(c, c->epi)) ? LOOP_ASM : LOOP_CXX;
-  if ((o.inner_loop == NBX_LOOP_ASM || o.inner_loop == NBX_LOOP_ASM_TS || o.inner_loop == NBX_LOOP_ASM_PF) && c->loop != LOOP_ASM)
-    return fail(NBX_ERR_ARG, "nbx_create: no hand-scheduled loop for this shape (needs fp32; kernel_variant SGPR with 1, 2 or 4 bodies per lane, SGPRW with j_per_split a multiple of 256 and 2 or 4 bodies per lane, or JLANE with 2, 4 or 8 bodies per wave)");
-  // Time-sliced wave priority (LOOP_ASM_TS) exists for the row-epilogue SGPR kernel: one workgroup row, every wave resident
-  // from the first cycle to the last.  Auto takes it when the fullest CU holds exactly two workgroups, i.e. two waves per
-  // SIMD: measured +4.5 % at 512 workgroups, +2.7 % at 384, -0.6 % with one wave per SIMD (nobody to alternate with, six
-  // more scalar instructions per trip) and -0.6 ... +0.3 % with three, four or eight (profiles/r02_time_sliced_ab.txt).
-  {
-    const bool ts_shape = c->loop == LOOP_ASM && c->variant == NBX_KERNEL_SGPR && c->epi == EPI_ROW && c->B >= 2;
-    if (o.inner_loop == NBX_LOOP_ASM_TS && !ts_shape)
-      return fail(NBX_ERR_ARG, "nbx_create: NBX_LOOP_ASM_TS needs the single-row SGPR kernel (reference summation order or j_split 1, fp32, 2 or 4 bodies per lane)");
-    const int cus = c->prop.multiProcessorCount > 0 ? c->prop.multiProcessorCount : 256;
-    const bool two_per_simd = (int)c->grid.x > cus && (int)c->grid.x <= 2 * cus;
-    if (ts_shape && (o.inner_loop == NBX_LOOP_ASM_TS || (o.inner_loop == NBX_LOOP_AUTO && two_per_simd))) c->loop = LOOP_ASM_TS;
-    // L2 prefetch (LOOP_ASM_PF): the same kernels when the launch leaves one wave per SIMD -- a rank that owns 131072 of 1M bodies:
-    // +3.5 %; with two or more waves per SIMD the other waves are the cover and it costs 0.4-1.4 % (profiles/r04_b2_prefetch_ab.txt)
-    if (o.inner_loop == NBX_LOOP_ASM_PF && !ts_shape)
-      return fail(NBX_ERR_ARG, "nbx_create: NBX_LOOP_ASM_PF needs the single-row SGPR kernel (reference summation order or j_split 1, fp32, 2 or 4 bodies per lane)");
-    if (ts_shape && (o.inner_loop == NBX_LOOP_ASM_PF || (o.inner_loop == NBX_LOOP_AUTO && (int)c->grid.x <= cus))) c->loop = LOOP_ASM_PF;
-  }
+  const char* msg = nullptr;
+  if (plan_launch({n, c->n_alloc, c->i_count, precision, c->prop.multiProcessorCount, c->own_stream}, o, &c->plan, &msg) != NBX_OK)
+    return fail(NBX_ERR_ARG, msg);
+  const int step_k = instance_index(c->plan.step), accel_k = instance_index(c->plan.accel);
+  if (step_k < 0 || accel_k < 0) return fail(NBX_ERR_ARG, "no kernel instance for this bodies_per_lane / precision");
+  c->launch_step = kLaunchers[step_k];
+  c->launch_accel = kLaunchers[accel_k];
   c->slice_bit = kSliceBit;
   if (const char* e = getenv("NBX_SLICE_BIT")) {  // experiments: log2 of the slice length in 10 ns units
     const int k = atoi(e);
     if (k >= 4 && k <= 30) c->slice_bit = 1u << k;
-  }
-  // The jlane kernel's generated loop keeps four records per set in flight; with few bodies per wave that is too little
-  // arithmetic to cover an L2 round trip when a SIMD holds a single wave, and the compiled loop (eight records per set) is
-  // 3-4 % ahead there (profiles/r02_jlane_ab.txt).  Auto takes the generated loop where it measured faster: 8 bodies per wave,
-  // or 4 with more than one wave per SIMD.
-  if (o.inner_loop == NBX_LOOP_AUTO && c->variant == NBX_KERNEL_JLANE && c->loop == LOOP_ASM) {
-    const int cus = c->prop.multiProcessorCount > 0 ? c->prop.multiProcessorCount : 256;
-    const bool several_waves = ceil_div(c->i_count, c->B) > cus * 4;
-    if (!(c->B == 8 || (c->B == 4 && several_waves))) c->loop = LOOP_CXX;
-  }
-  // use_graph: 0 auto (launch-bound sizes only: < ~0.3 ms of pair work per step), 1 on, 2 off;
-  // capture needs a stream of our own
-  {
-    const double pairs = (double)c->i_count * (double)c->n;
-    c->use_graph = c->own_stream && (o.use_graph == 1 || (o.use_graph == 0 && pairs < 1.5e9));
   }
 
   // + spare records: the pipelined SGPR loop requests one batch past the last split (never used)
@@ -696,11 +345,11 @@ int nbx_create(nbx_ctx** out, int32_t n, int32_t precision, const nbx_opts* opts
   CREATE_TRY(hipMalloc(&c->posm[0], pos_bytes));
   CREATE_TRY(hipMalloc(&c->posm[1], pos_bytes));
   CREATE_TRY(hipMalloc(&c->velm, c->rec * (size_t)c->own_pad));
-  CREATE_TRY(hipMalloc(&c->accp, c->rec * (size_t)c->own_pad * c->S));
-  const int max_parts = std::max(ceil_div(c->i_count, kBlock), (int)c->grid.x);
+  CREATE_TRY(hipMalloc(&c->accp, c->rec * (size_t)c->own_pad * c->plan.S));
+  const int max_parts = std::max(ceil_div(c->i_count, kBlock), c->plan.grid_x);
   CREATE_TRY(hipMalloc(&c->ke_part, sizeof(double) * (size_t)max_parts));
-  if (c->variant == NBX_KERNEL_EXACT || c->variant == NBX_KERNEL_EXACT_FMA) CREATE_TRY(hipMalloc(&c->mass_all, (c->rec / 4) * (size_t)c->n_alloc));
-  if (c->loop == LOOP_ASM && jpair_shape(c)) {  // same size and the same zero-filled spare records as posm
+  if (c->plan.variant == NBX_KERNEL_EXACT || c->plan.variant == NBX_KERNEL_EXACT_FMA) CREATE_TRY(hipMalloc(&c->mass_all, (c->rec / 4) * (size_t)c->n_alloc));
+  if (c->plan.pairs) {  // same size and the same zero-filled spare records as posm
     CREATE_TRY(hipMalloc(&c->posm_pairs, pos_bytes));
     CREATE_TRY(hipMemsetAsync(c->posm_pairs, 0, pos_bytes, c->stream));
   }
@@ -773,7 +422,7 @@ static int step_common(nbx_ctx* c, double dt, int32_t nsteps, double* ke_last, d
     if (rc) return rc;
   }
   int first = 0;
-  if (c->use_graph && !ke_trace && !c->profiling && nsteps >= 4) {
+  if (c->plan.use_graph && !ke_trace && !c->profiling && nsteps >= 4) {
     const int unit = std::min(nsteps & ~1, 50);  // one replay costs the host 10-16 us: 50 steps per replay keeps that under 0.3 us per step
     hipGraphExec_t exec = nullptr;
     rc = graph_unit_exec(c, unit, dt, &exec);
@@ -961,17 +610,18 @@ int nbx_stats(nbx_ctx* c, nbx_stats_t* s) {
   }
   std::memset(s, 0, sizeof(*s));
   s->n = c->n; s->n_alloc = c->n_alloc; s->i_begin = c->i_begin; s->i_count = c->i_count;
-  s->precision = c->precision; s->bodies_per_lane = c->B; s->j_split = c->S; s->j_tile = kTile;
-  s->kernel_variant = c->variant; s->fused_epilogue = c->epi; s->summation_order = c->order;
-  s->force_grid_x = c->grid.x; s->force_grid_y = c->grid.y; s->force_block = kBlock;
+  const nbx::Plan& p = c->plan;
+  s->precision = c->precision; s->bodies_per_lane = p.B; s->j_split = p.S; s->j_tile = kTile;
+  s->kernel_variant = p.variant; s->fused_epilogue = p.epi; s->summation_order = p.order;
+  s->force_grid_x = p.grid_x; s->force_grid_y = p.grid_y; s->force_block = kBlock;
   s->cu_count = c->prop.multiProcessorCount; s->clock_mhz = c->prop.clockRate / 1000;
   s->steps_done = c->steps_done;
   s->force_launches_timed = c->force_timed;
   s->force_ms_total = c->force_ms_total;
   s->pairs_per_launch = (double)c->i_count * (double)c->n;
   s->graph_replays = c->graph_replays;
-  s->use_graph = c->use_graph ? 1 : 0;
-  s->inner_loop = c->loop == LOOP_ASM_TS ? NBX_LOOP_ASM_TS : c->loop == LOOP_ASM_PF ? NBX_LOOP_ASM_PF : c->loop == LOOP_ASM ? NBX_LOOP_ASM : NBX_LOOP_CXX;
+  s->use_graph = p.use_graph ? 1 : 0;
+  s->inner_loop = p.loop == LOOP_ASM_TS ? NBX_LOOP_ASM_TS : p.loop == LOOP_ASM_PF ? NBX_LOOP_ASM_PF : p.loop == LOOP_ASM ? NBX_LOOP_ASM : NBX_LOOP_CXX;
   // some boxes report an empty marketing name; fall back to / append the ISA name
   std::snprintf(s->device_name, sizeof(s->device_name), "%s%s%s", c->prop.name, c->prop.name[0] ? " " : "",
                 c->prop.gcnArchName);
@@ -981,4 +631,3 @@ int nbx_stats(nbx_ctx* c, nbx_stats_t* s) {
 
 }  // extern "C"
 
-static_assert(nbx::kTile == 256 && nbx::kBlock == 256, "nbx_group.hip aligns blocks to the kernels' 256-record j tile");

@@ -24,7 +24,7 @@ using namespace nbx_detail;
 
 namespace {
 constexpr double kRcclInitAllowanceSeconds = 30.0;  // added to the collective timeout for ncclCommInitRank (see there)
-constexpr int kTile = 256;  // records per block alignment (= nbx::kTile: j tile of the kernels; checked in nbx_api.hip)
+using nbx::kTile;  // blocks are whole j tiles of the kernels
 }  // namespace
 
 // =============================================================================================

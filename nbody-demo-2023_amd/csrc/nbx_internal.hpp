@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/nbx_diag.h"  // includes nbx.h
+#include "nbx_plan.hpp"               // ceil_div, round_up, nbx::Plan
 
 namespace nbx_detail {
 
@@ -41,15 +42,13 @@ inline int guarded(const char* where, F&& body) noexcept {
   }
 }
 
-inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
-
 }  // namespace nbx_detail
 
 struct nbx_ctx {
   int n = 0, n_alloc = 0, i_begin = 0, i_count = 0, own_pad = 0, precision = 32;
-  int B = 1, S = 1, jps = 0, variant = NBX_KERNEL_LDS, epi = 0 /* nbx::EPI_SLAB */, math = 0 /* nbx::MATH_SCALAR */, order = NBX_ORDER_TREE;
-  int loop = 0;  // nbx::LOOP_CXX; nbx::LOOP_ASM where the hand-scheduled j loop is in use; nbx::LOOP_ASM_TS with time-sliced wave priority
+  nbx::Plan plan;  // launch shape and kernel instances (nbx_plan.hpp)
+  void (*launch_step)(nbx_ctx*, double dt, int acc_only) = nullptr;  // plan.step and plan.accel, resolved by nbx_create
+  void (*launch_accel)(nbx_ctx*, double dt, int acc_only) = nullptr;
   unsigned slice_bit = 0;  // LOOP_ASM_TS: clock bit of the priority slices
   int device = 0;
   hipStream_t stream = nullptr;
@@ -75,9 +74,7 @@ struct nbx_ctx {
   double force_ms_total = 0.0;
   long long force_timed = 0;
   hipDeviceProp_t prop{};
-  dim3 grid;
-  // hipGraph replay of multi-step windows (launch-bound small n)
-  bool use_graph = false;
+  // hipGraph replay of multi-step windows (launch-bound small n; plan.use_graph)
   struct GraphUnit { int steps; int parity; double dt; hipGraphExec_t exec; };
   std::vector<GraphUnit> graphs;
   long long graph_replays = 0;

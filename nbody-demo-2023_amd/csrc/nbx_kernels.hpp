@@ -31,7 +31,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "nbx_pair.hpp"  // kBlock, kTile, V4, the pair term, euler_update, block_sum
+#include "nbx_pair.hpp"  // V4, the pair term, euler_update, block_sum
+#include "nbx_plan.hpp"  // kBlock, kTile, the shape enums JSRC_*, MATH_*, LOOP_*, EPI_* (what they mean: there)
 
 namespace nbx {
 
@@ -51,7 +52,6 @@ struct ForceArgs {
   unsigned slice_bit;                // LOOP_ASM_TS: clock bit of the priority slices (kSliceBit unless NBX_SLICE_BIT overrides)
 };
 
-enum : int { JSRC_LDS = 1, JSRC_SGPR = 2 };
 // records per scalar-load batch of the SGPR source (one s_load_dwordx16 = 64 B); a split's j range
 // (a quarter of it under WSPLIT) must be a multiple of this
 template <typename T> constexpr int kSgprBatch = 64 / (4 * (int)sizeof(T));
@@ -96,36 +96,11 @@ __device__ __forceinline__ void sgpr_wait(SgprBatch<T> (&b)[G]) {
   else asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(b[0].r), "+s"(b[1].r));
 }
 
-enum : int { MATH_SCALAR = 0, MATH_PACKED = 1 };
-// How the SGPR kernel's j loop is scheduled: LOOP_CXX = hipcc schedules the C++ loop below; LOOP_ASM = the hand-scheduled
-// gfx950 loop of nbx_sgpr_loop.inc (packed fp32, B = 2 or 4, no wave split): same operations in the same order, hence
-// the same bits (tests compare the two), but no s_mov splats, one pointer update per trip and 8-byte aligned VOP3P code:
-// worth 13 % when a SIMD holds a single wave, where every scalar instruction costs a full 4-cycle issue slot.
-// With ONE body per lane LOOP_ASM is the two-j-records-per-packed-operation loop (sgpr_loop_asm_jpair): slices that leave less than
-// one wave per SIMD at two bodies per lane (<= 65536 owned bodies) get twice the waves at 76 cycles per two pairs instead of 2 x 56;
-// it reads the pair-interleaved copy of the records that pair_transpose_kernel rebuilds every step.
-// LOOP_ASM_TS = the same loop with time-sliced wave priority, for shapes that put two waves on a SIMD for the whole launch
-// (reference order, grid.y == 1, 257..512 workgroups on 256 CUs): this chip issues the waves of a SIMD in strict age order,
-// so without it they run one after the other -- the older one leaves the loop at 0.50 of the kernel time -- and the younger
-// one has nobody to fill its issue bubbles (tools/wave_fair.hip).  +4.5 % at n = 262144; nothing to gain
-// with one wave per SIMD (-0.6 %: the six scalar instructions) or with three and more (profiles/r02_time_sliced_ab.txt).
-// LOOP_ASM_PF = the same loop plus one L2-prefetch load per trip, for launches that leave ONE wave per SIMD (grid.x <= CUs, e.g. a rank
-// that owns 131072 of 1M bodies): there the arithmetic of one ring group (512 cycles) is all the cover a scalar load gets, every wave of
-// an XCD asks for the same line at about the same time, and what they all wait for is the first requester's Infinity-Cache round trip
-// (~545 cycles).  +3.5 % at one wave per SIMD, -0.4 ... -1.4 % with two or more (profiles/r04_b2_prefetch_ab.txt).
-enum : int { LOOP_CXX = 0, LOOP_ASM = 1, LOOP_ASM_TS = 2, LOOP_ASM_PF = 3 };
 // clock bit (s_memrealtime counts 10 ns) that selects the favoured slot parity: slices of 2^16 x 10 ns = 0.66 ms.  Measured
 // 2^14 ... 2^19 within 1 % of each other, 2^16-2^17 best; shorter slices lose to the time the unfavoured wave needs to reach
 // its next decision, longer ones to the imbalance of the last slice.
 constexpr unsigned kSliceBit = 1u << 16;
 #include "nbx_sgpr_loop.inc"
-// What a workgroup does with its accelerations:
-//   EPI_SLAB  write them to its split's slab (the separate integrate_kernel, or nbx_accel, consumes the slabs)
-//   EPI_ROW   single split (gridDim.y == 1): integrate its bodies directly, no slab
-// (Round 1 also had a "last arriver integrates" epilogue for split shapes -- agent-scope release / ticket / acquire.  It was
-// bit-equal but slower than the extra launch at every size, and force_jlane_kernel below now gives launch-bound sizes
-// their single launch per step without any inter-workgroup hand-off; it was removed.)
-enum : int { EPI_SLAB = 0, EPI_ROW = 1 };
 
 // The B i-bodies a lane keeps in registers, and how one j record is applied to them.
 template <typename T, int B, int MATH>

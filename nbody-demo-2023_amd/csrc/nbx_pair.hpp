@@ -5,10 +5,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace nbx {
+#include "nbx_plan.hpp"  // kBlock, kTile
 
-constexpr int kBlock = 256;  // threads per workgroup
-constexpr int kTile = 256;   // j records per LDS tile (BASELINE.json configs[1]: "LDS j-tile=256")
+namespace nbx {
 
 template <typename T> struct V4;
 template <> struct V4<float> { using type = float4; };

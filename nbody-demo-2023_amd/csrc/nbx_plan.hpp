@@ -1,0 +1,374 @@
+// nbx_plan.hpp -- which force kernel a context runs and with what launch shape: the policy of nbx_create, host-only.
+// Standard library and include/nbx.h only: no HIP call, no environment, no nbx_ctx, so that g++ compiles it without ROCm
+// (tests/test_launch_plan.py drives it with every nbx_opts).  kInstances is the one list of compiled force-kernel instances:
+// nbx_api.hip instantiates exactly those and launches the ones plan_launch names.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+
+#include "../../include/nbx.h"
+
+namespace nbx_detail {
+inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
+}  // namespace nbx_detail
+
+namespace nbx {
+using nbx_detail::ceil_div;
+using nbx_detail::round_up;
+
+constexpr int kBlock = 256;  // threads per workgroup
+constexpr int kTile = 256;   // j records per LDS tile (BASELINE.json configs[1]: "LDS j-tile=256")
+// j-range granule of the plain SGPR kernel: whole trips of every hand-scheduled loop (nbx_api.hip checks it against kSgprAsmTrip<>)
+constexpr int kSgprGran = 256;
+
+enum : int { JSRC_LDS = 1, JSRC_SGPR = 2 };
+enum : int { MATH_SCALAR = 0, MATH_PACKED = 1 };
+// How the SGPR kernel's j loop is scheduled: LOOP_CXX = hipcc schedules force_kernel's C++ loop; LOOP_ASM = the hand-scheduled
+// gfx950 loop of nbx_sgpr_loop.inc (packed fp32, B = 2 or 4, no wave split): same operations in the same order, hence
+// the same bits (tests compare the two), but no s_mov splats, one pointer update per trip and 8-byte aligned VOP3P code:
+// worth 13 % when a SIMD holds a single wave, where every scalar instruction costs a full 4-cycle issue slot.
+// With ONE body per lane LOOP_ASM is the two-j-records-per-packed-operation loop (sgpr_loop_asm_jpair): slices that leave less than
+// one wave per SIMD at two bodies per lane (<= 65536 owned bodies) get twice the waves at 76 cycles per two pairs instead of 2 x 56;
+// it reads the pair-interleaved copy of the records that pair_transpose_kernel rebuilds every step.
+// LOOP_ASM_TS = the same loop with time-sliced wave priority, for shapes that put two waves on a SIMD for the whole launch
+// (reference order, grid.y == 1, 257..512 workgroups on 256 CUs): this chip issues the waves of a SIMD in strict age order,
+// so without it they run one after the other -- the older one leaves the loop at 0.50 of the kernel time -- and the younger
+// one has nobody to fill its issue bubbles (tools/wave_fair.hip).  +4.5 % at n = 262144; nothing to gain
+// with one wave per SIMD (-0.6 %: the six scalar instructions) or with three and more (profiles/r02_time_sliced_ab.txt).
+// LOOP_ASM_PF = the same loop plus one L2-prefetch load per trip, for launches that leave ONE wave per SIMD (grid.x <= CUs, e.g. a rank
+// that owns 131072 of 1M bodies): there the arithmetic of one ring group (512 cycles) is all the cover a scalar load gets, every wave of
+// an XCD asks for the same line at about the same time, and what they all wait for is the first requester's Infinity-Cache round trip
+// (~545 cycles).  +3.5 % at one wave per SIMD, -0.4 ... -1.4 % with two or more (profiles/r04_b2_prefetch_ab.txt).
+enum : int { LOOP_CXX = 0, LOOP_ASM = 1, LOOP_ASM_TS = 2, LOOP_ASM_PF = 3 };
+// What a workgroup does with its accelerations:
+//   EPI_SLAB  write them to its split's slab (the separate integrate_kernel, or nbx_accel, consumes the slabs)
+//   EPI_ROW   single split (gridDim.y == 1): integrate its bodies directly, no slab
+// (Round 1 also had a "last arriver integrates" epilogue for split shapes -- agent-scope release / ticket / acquire.  It was
+// bit-equal but slower than the extra launch at every size, and force_jlane_kernel now gives launch-bound sizes
+// their single launch per step without any inter-workgroup hand-off; it was removed.)
+enum : int { EPI_SLAB = 0, EPI_ROW = 1 };
+
+// NBX_ORDER_AUTO: fp32 sums of more terms than this use the reference's order.  131072 x 500 steps agrees with the
+// reference to 2e-5 in tree order (profiles/r01_validate_orders_n131072_s500.log); 262144 x 200 does not (1.3e-3).
+constexpr int kTreeOrderMaxN = 131072;
+// NBX_KERNEL_AUTO, tree order: contexts that own at most this many bodies step with ONE launch (force_jlane_kernel)
+// (12288: 41 us against SGPRW's 48.  Round 3, profiles/r03_band_sweep.txt: between 12288 and 16384 the wave-split kernel falls back
+// to two bodies per lane and, at sizes whose splits are not whole tiles, to the compiled loop -- 40-45 % -- while the one-launch kernel
+// with 8 bodies per wave is 6-15 % ahead: 13000 50.3 vs 53.2 us, 15000 58.0 vs 65.6, 16000 62.8 vs 72.3.)  16384 ITSELF is excluded:
+// there the two tie within 2 %, and SGPRW's summation tree (S = 32) is the one whose chaotic n = 16384 x 500 run -- BASELINE
+// configs[1] -- stays inside the 1e-4 gate at every printed step (profiles/r02_config1_by_kernel.txt, r03_config1_by_shape.txt).
+constexpr int kJlaneMaxOwn = 16383;
+// Tree order, wave-split kernel: contexts that own up to this many bodies keep round 1's split rule (S = 32 at 16384).  Fewer
+// splits are 5 % faster there (profiles/r03_band_sweep.txt: S = 4 or 8), but BASELINE.json configs[1] -- n = 16384 x 500 steps, 450 of
+// them after the bounce -- is decided at the reference's own noise level, and of S = 2, 4, 8, 16, 32 only the tree of S = 32
+// lands inside 1e-4 at every printed row (7.7e-5; the others 1.05e-4 ... 1.43e-4, two builds of the reference itself 1.3e-4:
+// profiles/r03_config1_by_shape.txt).  tests/test_parity_gpu.py::test_config1_launch_shape_is_frozen pins it.
+constexpr int kRound1SplitMaxOwn = 16384;
+constexpr int kJlaneMaxOwnF64 = 12288;  // fp64 form: 92 us against 97 at 12288, SGPRW ahead at 16384 (profiles/r02_jlane_f64_ab.txt)
+
+// One compiled force-kernel instance: its template arguments.  INST_FORCE = force_kernel<T, B, jsrc, epi, 1, math, ws, loop>;
+// INST_JLANE = force_jlane_kernel<B, D, loop> (fp32) or force_jlane_kernel_f64<B, D> (B = bodies per wave); INST_EXACT =
+// force_exact_kernel<T, B == 1> (B = 1: FMA contraction, NBX_KERNEL_EXACT_FMA).  Fields a kernel does not take are 0.
+enum : int { INST_FORCE = 0, INST_JLANE = 1, INST_EXACT = 2 };
+struct Instance {
+  int kind, precision, B, jsrc, epi, math;
+  bool ws;
+  int loop;
+};
+constexpr bool operator==(const Instance& a, const Instance& b) {
+  return a.kind == b.kind && a.precision == b.precision && a.B == b.B && a.jsrc == b.jsrc && a.epi == b.epi && a.math == b.math &&
+         a.ws == b.ws && a.loop == b.loop;
+}
+namespace instance_list {  // {kind, precision, B, jsrc, epi, math, ws, loop}
+constexpr int F = INST_FORCE, J = INST_JLANE, X = INST_EXACT, S_ = JSRC_SGPR, L_ = JSRC_LDS, R_ = EPI_ROW, Z_ = EPI_SLAB, SC = MATH_SCALAR,
+              PK = MATH_PACKED, CXX = LOOP_CXX, ASM = LOOP_ASM, TS = LOOP_ASM_TS, PF = LOOP_ASM_PF;
+constexpr Instance kInstances[] = {
+    // compiled loop: fp32 one body per lane, fp64 1, 2 and 4 (scalar math); fp32 2, 4 and (no wave split) 8 on the packed pipe
+    {F, 32, 1, S_, Z_, SC, true, CXX}, {F, 32, 1, S_, R_, SC, false, CXX}, {F, 32, 1, S_, Z_, SC, false, CXX}, {F, 32, 1, L_, R_, SC, false, CXX}, {F, 32, 1, L_, Z_, SC, false, CXX},
+    {F, 64, 1, S_, Z_, SC, true, CXX}, {F, 64, 1, S_, R_, SC, false, CXX}, {F, 64, 1, S_, Z_, SC, false, CXX}, {F, 64, 1, L_, R_, SC, false, CXX}, {F, 64, 1, L_, Z_, SC, false, CXX},
+    {F, 64, 2, S_, Z_, SC, true, CXX}, {F, 64, 2, S_, R_, SC, false, CXX}, {F, 64, 2, S_, Z_, SC, false, CXX}, {F, 64, 2, L_, R_, SC, false, CXX}, {F, 64, 2, L_, Z_, SC, false, CXX},
+    {F, 64, 4, S_, Z_, SC, true, CXX}, {F, 64, 4, S_, R_, SC, false, CXX}, {F, 64, 4, S_, Z_, SC, false, CXX}, {F, 64, 4, L_, R_, SC, false, CXX}, {F, 64, 4, L_, Z_, SC, false, CXX},
+    {F, 32, 2, S_, Z_, PK, true, CXX}, {F, 32, 2, S_, R_, PK, false, CXX}, {F, 32, 2, S_, Z_, PK, false, CXX}, {F, 32, 2, L_, R_, PK, false, CXX}, {F, 32, 2, L_, Z_, PK, false, CXX},
+    {F, 32, 4, S_, Z_, PK, true, CXX}, {F, 32, 4, S_, R_, PK, false, CXX}, {F, 32, 4, S_, Z_, PK, false, CXX}, {F, 32, 4, L_, R_, PK, false, CXX}, {F, 32, 4, L_, Z_, PK, false, CXX},
+    {F, 32, 8, S_, R_, PK, false, CXX}, {F, 32, 8, S_, Z_, PK, false, CXX}, {F, 32, 8, L_, R_, PK, false, CXX}, {F, 32, 8, L_, Z_, PK, false, CXX},
+    // hand-scheduled loops (fp32, SGPR source): two j records per operation for one body per lane, 2 and 4 bodies per lane with and
+    // without the wave split; time-sliced priority and L2 prefetch for the single-row kernel
+    {F, 32, 1, S_, R_, SC, false, ASM}, {F, 32, 1, S_, Z_, SC, false, ASM},
+    {F, 32, 2, S_, Z_, PK, true, ASM}, {F, 32, 2, S_, R_, PK, false, ASM}, {F, 32, 2, S_, Z_, PK, false, ASM},
+    {F, 32, 4, S_, Z_, PK, true, ASM}, {F, 32, 4, S_, R_, PK, false, ASM}, {F, 32, 4, S_, Z_, PK, false, ASM},
+    {F, 32, 2, S_, R_, PK, false, TS}, {F, 32, 4, S_, R_, PK, false, TS}, {F, 32, 2, S_, R_, PK, false, PF}, {F, 32, 4, S_, R_, PK, false, PF},
+    // one launch per step: fp32 2, 4, 8 (generated loop or compiled) and 16 bodies per wave, fp64 2, 4, 8
+    {J, 32, 2, 0, 0, 0, false, ASM}, {J, 32, 2, 0, 0, 0, false, CXX}, {J, 32, 4, 0, 0, 0, false, ASM}, {J, 32, 4, 0, 0, 0, false, CXX},
+    {J, 32, 8, 0, 0, 0, false, ASM}, {J, 32, 8, 0, 0, 0, false, CXX}, {J, 32, 16, 0, 0, 0, false, CXX},
+    {J, 64, 2, 0, 0, 0, false, CXX}, {J, 64, 4, 0, 0, 0, false, CXX}, {J, 64, 8, 0, 0, 0, false, CXX},
+    // the reference's arithmetic (validation)
+    {X, 32, 0, 0, 0, 0, false, CXX}, {X, 32, 1, 0, 0, 0, false, CXX}, {X, 64, 0, 0, 0, 0, false, CXX}, {X, 64, 1, 0, 0, 0, false, CXX},
+};
+}  // namespace instance_list
+using instance_list::kInstances;
+constexpr int kInstanceCount = (int)(sizeof(kInstances) / sizeof(kInstances[0]));
+// position of k in kInstances, -1 if it is not compiled
+constexpr int instance_index(const Instance& k) {
+  for (int i = 0; i < kInstanceCount; ++i)
+    if (kInstances[i] == k) return i;
+  return -1;
+}
+
+// A context's launch plan (nbx_create; nbx_stats reports it).
+struct Plan {
+  int variant = NBX_KERNEL_LDS, order = NBX_ORDER_TREE;
+  int B = 1, S = 1, jps = 0;  // bodies per lane (per wave: JLANE), j-splits, j records per split
+  int math = MATH_SCALAR, epi = EPI_SLAB, loop = LOOP_CXX;
+  int grid_x = 0, grid_y = 1;
+  bool use_graph = false;  // nbx_step replays multi-step windows from a hipGraph
+  bool pairs = false;      // one body per lane + hand-scheduled loop: the pair-interleaved copy of the records is rebuilt every step
+  Instance step{}, accel{};  // the step kernel, and nbx_accel's form of it (accelerations into the slabs, nothing integrated)
+};
+
+// The instance a plan launches with inner loop `loop`.  nbx_accel's slab form of a single-row context: the plain hand-scheduled loop.
+inline Instance plan_instance(const Plan& p, int precision, bool accel, int loop) {
+  if (p.variant == NBX_KERNEL_EXACT || p.variant == NBX_KERNEL_EXACT_FMA)
+    return {INST_EXACT, precision, p.variant == NBX_KERNEL_EXACT_FMA ? 1 : 0, 0, 0, 0, false, loop};
+  if (p.variant == NBX_KERNEL_JLANE) return {INST_JLANE, precision, p.B, 0, 0, 0, false, loop};
+  if (accel && (loop == LOOP_ASM_TS || loop == LOOP_ASM_PF)) loop = LOOP_ASM;
+  return {INST_FORCE, precision, p.B, p.variant == NBX_KERNEL_LDS ? JSRC_LDS : JSRC_SGPR, accel ? EPI_SLAB : p.epi, p.math,
+          p.variant == NBX_KERNEL_SGPRW, loop};
+}
+
+// Bodies per lane of the reference-order kernel (one chain per owned body, S = 1).  Its run time is quantised: the
+// ceil(own / (256 B)) workgroups are spread over the CUs, and a launch takes as long as the fullest CU, which holds
+// r = ceil(workgroups / CUs) of them.  Measured on MI355X at n = 1048576 with the hand-scheduled loop for B = 2 and 4
+// (profiles/r02_reference_order_thresholds.txt), ms for r = 1, 2, 3, ...: B = 1, compiled loop: 31.0, 48.6, 70.3, 91, 112 (plain VALU ops);
+// B = 2: 31.5 (30.0 with the L2 prefetch and the 256-record trips of LOOP_ASM_PF, round 4), 59.6, 88.5, 118;  B = 4: 59.3, 117.4, 175.6, 234.6 -- linear in r after
+// the first workgroup.  With two workgroups on the fullest CU the time-sliced loop applies (LOOP_ASM_TS): B = 2, r = 2 then costs 58.0
+// (profiles/r02_time_sliced_ab.txt: 57.98 ms for 262144 of 1M bodies), B = 4, r = 2 117.0.  Round 4: one body per lane with the
+// two-j-records-per-operation loop (sgpr_loop_asm_jpair, `jpair`): 17.9 for r = 1 (65536 of 1M bodies: 48.8 % of the roofline against 28.4 %
+// for the compiled loop and 27.8 % for B = 2 on half the CUs), 34.3 for r = 2 (profiles/r04_jpair_ab.txt) -- so it takes every slice of up to
+// 256 x CUs = 65536 bodies, and B = 2 keeps 65537 ... 131072.  Pick the B with the smallest estimate; ties go to the larger B (fewer
+// workgroups stream the j records).  Only the ratios matter, so the table serves every n.
+inline int reference_order_bodies_per_lane(int own, int cus, int max_b, bool jpair, double* cost_out = nullptr) {
+  struct Cost { int b; double first, next, two; };
+  static const Cost kCost[] = {{1, 31.0, 20.2, 0.0}, {2, 30.0, 29.25, 58.0}, {4, 59.8, 58.2, 117.0}};
+  static const Cost kJpair = {1, 17.9, 16.4, 0.0};  // one body per lane, two j records per packed operation
+  int best = 1;
+  double best_t = 0.0;
+  for (const auto& k0 : kCost) {
+    const auto& k = (k0.b == 1 && jpair) ? kJpair : k0;
+    if (k.b > max_b) continue;
+    const int wgs = ceil_div(own, kBlock * k.b);
+    const int r = std::max(1, ceil_div(wgs, std::max(1, cus)));
+    const double t = (r == 2 && k.two > 0.0) ? k.two : k.first + k.next * (r - 1);
+    if (best_t == 0.0 || t <= best_t * 1.01) { best = k.b; best_t = std::min(t, best_t == 0.0 ? t : best_t); }
+  }
+  // Where two bodies per lane load every CU evenly too (twice the workgroups, all CUs with the same count), they win over four
+  // by 2.5 % at 262144 owned bodies and tie from 524288 up (the younger wave of a SIMD fills the older one's issue bubbles;
+  // profiles/r02_loop_ab_asm_vs_cxx.txt, same process on two boxes): take them.
+  if (best == 4 && max_b >= 2 && ceil_div(own, kBlock * 2) % std::max(1, cus) == 0) best = 2;
+  if (cost_out) *cost_out = best_t;
+  return best;
+}
+
+// What one force launch of this plan would cost, in relative units, if the context owned `own` bodies instead: the cost table of
+// reference_order_bodies_per_lane in reference order (a step function of `own`: the launch lasts as long as its fullest CU), and `own`
+// itself in tree order, where j-splits keep the time close to proportional.  The tuner of nbx_group_retune uses the RATIO of two such
+// values to predict what a move of the shares would do before it makes it (nbx_detail::model_force_cost).
+inline double force_cost(const Plan& p, int precision, int cus, int own) {
+  if (own <= 0) return 0.0;
+  if (p.order != NBX_ORDER_REFERENCE) return (double)own;
+  const bool jpair = precision == 32 && p.variant == NBX_KERNEL_SGPR;
+  double t = 0.0;
+  (void)reference_order_bodies_per_lane(own, cus > 0 ? cus : 256, precision == 32 ? 8 : 4, jpair, &t);
+  return t;
+}
+
+// j-splits of the wave-split kernel with the hand-scheduled loop (round 3, profiles/r03_band_sweep.txt).  Round 1's rule -- 32
+// workgroups per CU, i.e. S = 32 up to n = 65536 -- suited the compiler-scheduled loop, which needed eight waves per SIMD to
+// hide its own bubbles.  The hand-scheduled loop is at its rate with two, and every extra split costs a slab write, a slab
+// read by integrate_kernel and a shorter j loop per wave.  The launch lasts as long as the fullest CU: ceil(bi S / CUs)
+// workgroups of 1/S of the j range each.  Take the S (power of two) that minimises that product; among equals the smallest
+// S that still gives every CU two workgroups.  Measured optimum at every size tried: 24576 -> 8 (+2.6 % over S = 32),
+// 32768 -> 4 (+1.9 %), 49152 -> 4 (+1.2 %), 65536 -> 2 (+1.2 %); three workgroups on half the CUs (24576 with S = 4) is 20 % slower.
+inline int balanced_j_split(int bi, int cus, int max_s) {
+  double best_cost = 0.0;
+  for (int S = 1; S <= max_s; S *= 2) {
+    const double cost = (double)ceil_div(bi * S, cus) / S;
+    if (best_cost == 0.0 || cost < best_cost) best_cost = cost;
+  }
+  int pick = 0, largest = 1;
+  for (int S = 1; S <= max_s; S *= 2) {
+    if ((double)ceil_div(bi * S, cus) / S > best_cost * 1.0001) continue;
+    largest = S;
+    if (!pick && bi * S >= 2 * cus) pick = S;
+  }
+  return pick ? pick : largest;
+}
+
+// What the shape rules read: the context as nbx_create resolved it (n_alloc rounded to the tile, i_count of a whole run = n), the
+// device's CU count (<= 0: taken as 256) and whether the context owns its stream (a caller's stream is not captured for replay).
+struct PlanInput { int n, n_alloc, i_count, precision, cus; bool own_stream; };
+
+// Launch shape.  Measured with tools/kbench on MI355X (profiles/r01_kbench_*): the force kernel is
+// VALU-issue bound and wants all 8 wave slots of every SIMD filled, i.e. >= 8192 workgroups of 256
+// threads (32 per CU).  Fastest shape from n = 2k to 1M: j records in SGPRs, the four waves of a
+// workgroup sharing 64*B bodies and splitting the j range (NBX_KERNEL_SGPRW), B = 4 bodies per lane
+// (two packed register pairs; B = 2 for short i ranges), plus S j-range splits across workgroups:
+// 58-60 % of the fp32 roofline at n >= 64k, 52 % at 16k, vs 52 % / 36 % for B = 8 / LDS tile.
+inline void auto_shape(Plan* c, const PlanInput& in, const nbx_opts& o) {
+  const int cus = in.cus > 0 ? in.cus : 256;
+  const int target_wgs = cus * 32;
+  int variant = o.kernel_variant;
+  if (variant == NBX_KERNEL_EXACT || variant == NBX_KERNEL_EXACT_FMA) {  // one thread per body, no blocking, no splits, separate integrate kernel
+    c->B = 1; c->S = 1; c->jps = in.n_alloc; c->math = MATH_SCALAR; c->variant = variant; c->epi = EPI_SLAB;
+    c->order = NBX_ORDER_REFERENCE;  // one accumulator per body, j ascending: it IS the reference's loop
+    c->grid_x = ceil_div(in.i_count, kBlock); c->grid_y = 1;
+    return;
+  }
+  // Summation order (include/nbx.h).  The reference adds a body's n terms one after the other into one fp32
+  // accumulator; from n = 262144 that sum carries ~1e-5 of rounding noise per step which heats the system (kenergy
+  // +5e-4..1e-3 against an fp64 run; 1.6e-5 over 500 steps at n = 131072).  A tree of partial sums does not reproduce
+  // that, a single accumulator per body in the same j order does (to 5e-5 / 5e-7, tools/validate_big.py) -- at the
+  // price of one chain per owned body.  The noise is a property of the LENGTH of the sum, i.e. of n, not of how many
+  // bodies this context owns: every rank of a sharded run takes the same decision.
+  int order = o.summation_order;
+  if (order != NBX_ORDER_REFERENCE && order != NBX_ORDER_TREE) {
+    const bool shape_given = o.j_split > 0 || variant == NBX_KERNEL_SGPRW || variant == NBX_KERNEL_JLANE;  // tree-only shapes
+    if (o.j_split == 1 && variant != NBX_KERNEL_SGPRW) order = NBX_ORDER_REFERENCE;
+    // fp64 keeps the tree: its summation noise (~1e-13) is far below the 1e-10 fp64 gate in either order
+    else order = (!shape_given && in.precision == 32 && in.n > kTreeOrderMaxN) ? NBX_ORDER_REFERENCE : NBX_ORDER_TREE;
+  }
+  c->order = order;
+  if (order == NBX_ORDER_REFERENCE) {
+    if (variant != NBX_KERNEL_LDS && variant != NBX_KERNEL_SGPR) variant = NBX_KERNEL_SGPR;
+    int B = o.bodies_per_lane;
+    const int maxBr = in.precision == 32 ? 8 : 4;
+    if (B != 1 && B != 2 && B != 4 && B != 8) B = 0;
+    if (B > maxBr) B = maxBr;
+    // fp32, plain SGPR kernel, hand-scheduled loops allowed: one body per lane means sgpr_loop_asm_jpair
+    const bool jpair = in.precision == 32 && variant == NBX_KERNEL_SGPR && o.inner_loop != NBX_LOOP_CXX;
+    if (B == 0) B = reference_order_bodies_per_lane(in.i_count, cus, maxBr, jpair);
+    c->B = B; c->S = 1; c->jps = in.n_alloc; c->variant = variant;
+    c->math = (in.precision == 32 && B >= 2) ? MATH_PACKED : MATH_SCALAR;
+    c->epi = o.fused_epilogue == 2 ? EPI_SLAB : EPI_ROW;
+    c->grid_x = ceil_div(in.i_count, kBlock * B); c->grid_y = 1;
+    return;
+  }
+  // Launch-bound sizes (fp32): one launch per step with the lanes of a wave splitting j (force_jlane_kernel).  Bodies per
+  // wave: the power of two that gives about one wave per SIMD (1024 waves), between 2 and 16.
+  const int max_nb = in.precision == 32 ? 16 : 8;  // fp64 bodies take two SGPRs per coordinate
+  const bool jlane_auto = variant == NBX_KERNEL_AUTO && o.j_split <= 0 && o.bodies_per_lane == 0 && o.fused_epilogue != 2 &&
+                          in.i_count <= (in.precision == 32 ? kJlaneMaxOwn : kJlaneMaxOwnF64);
+  if (variant == NBX_KERNEL_JLANE || jlane_auto) {
+    int NB = o.bodies_per_lane;
+    if ((NB != 2 && NB != 4 && NB != 8 && NB != 16) || NB > max_nb) {
+      // A launch lasts as long as the fullest SIMD: ceil(waves / SIMDs) rounds of NB bodies each, times what a body-round costs
+      // with that NB.  Measured per body-round and per j record, relative to NB = 8 (profiles/r03_jlane_band.txt: the same ratios
+      // at 12288, 13000 and 16383 bodies): 2 bodies per wave 1.29 (every wave streams all j records and transposes through LDS
+      // for two bodies only), 4 -> 1.06, 8 -> 1.00 (the generated loop), 16 -> 1.06 (compiled loop only).  Smallest product wins:
+      // 2048 -> 2, 4096 -> 4, 8192 -> 8, 12288 -> 4 (three full rounds), 13000 ... 16383 -> 8 -- the measured optimum at each.
+      // Round 2 counted body-rounds alone, which sent 13000 and 14336 to NB = 2 (56.6 us against 50.1 with 8).
+      // fp64 (no generated loop, other ratios not measured): body-rounds alone, ties to the larger NB, as in round 2.
+      long best = 0;
+      for (int nb = 2; nb <= max_nb; nb *= 2) {
+        const long weight = in.precision != 32 ? 100 : (nb == 2 ? 129 : nb == 8 ? 100 : 106);
+        const long cost = (long)ceil_div(ceil_div(in.i_count, nb), cus * 4) * nb * weight;
+        if (best == 0 || cost <= best) { best = cost; NB = nb; }
+      }
+    }
+    c->B = NB; c->S = 1; c->jps = in.n_alloc; c->math = in.precision == 32 ? MATH_PACKED : MATH_SCALAR; c->variant = NBX_KERNEL_JLANE; c->epi = EPI_ROW;
+    c->grid_x = ceil_div(ceil_div(in.i_count, NB), 4); c->grid_y = 1;
+    return;
+  }
+  if (variant != NBX_KERNEL_LDS && variant != NBX_KERNEL_SGPR && variant != NBX_KERNEL_SGPRW) variant = NBX_KERNEL_SGPRW;
+  const int maxB = (in.precision == 32 && variant != NBX_KERNEL_SGPRW) ? 8 : 4;
+  int B = o.bodies_per_lane;
+  if (B != 1 && B != 2 && B != 4 && B != 8) B = 0;
+  if (B > maxB) B = maxB;
+  if (B == 0) B = in.i_count >= 16384 ? 4 : 2;
+  const int iblk = (variant == NBX_KERNEL_SGPRW ? 64 : kBlock) * B;  // bodies per workgroup
+  // j-range granularity of one split: a whole LDS tile / two pipelined SGPR batches (per wave)
+  // (the hand-scheduled loop of the plain SGPR kernel walks whole trips of up to 64 records)
+  // (round 3: where the balanced split rule applies -- few, long splits -- a split is a whole number of 256-record tiles, so
+  // that every wave's quarter is whole trips of the hand-scheduled loop whatever n is: n = 50000 used to get 32 splits of 1568
+  // records and, with them, the compiler-scheduled loop)
+  // Only where tree order is what AUTO takes (n <= 131072).  Above that it runs on request alone -- asked for because it is closer to the
+  // true sum than the reference's single chain -- and the number of chains is what buys that: n = 262144 keeps its 8 x 4, 1M its 2 x 4.
+  const bool balanced = o.j_split <= 0 && in.precision == 32 && variant == NBX_KERNEL_SGPRW && in.i_count > kRound1SplitMaxOwn && in.n <= kTreeOrderMaxN;
+  const int gran = variant == NBX_KERNEL_LDS ? kTile : (variant == NBX_KERNEL_SGPR ? kSgprGran : (balanced ? 256 : 32));
+  const int max_split = std::max(1, in.n_alloc / gran);
+  int S = o.j_split;
+  if (S <= 0) {
+    const int bi = ceil_div(in.i_count, iblk);
+    if (balanced) S = balanced_j_split(bi, cus, std::min(32, max_split));
+    else S = std::min(32, ceil_div(target_wgs, bi));
+    // the S partial-acceleration slabs are written and re-read every step: keep them <= 256 MiB
+    const size_t own_pad = (size_t)round_up(in.i_count, kBlock), rec = in.precision == 32 ? 16 : 32;
+    while (S > 1 && (size_t)S * own_pad * rec > ((size_t)256 << 20)) S /= 2;
+  }
+  S = std::max(1, std::min(S, max_split));
+  int jps = round_up(ceil_div(in.n_alloc, S), gran);
+  S = ceil_div(in.n_alloc, jps);  // drop empty tail splits
+  c->B = B;
+  c->S = S;
+  c->jps = jps;
+  c->math = (in.precision == 32 && B >= 2) ? MATH_PACKED : MATH_SCALAR;
+  c->variant = variant;
+  // fused_epilogue: 0 auto, 1 on, 2 off.  A single split integrates directly (EPI_ROW); shapes with j-splits always
+  // use the separate integrate kernel (one launch per step for small n is NBX_KERNEL_JLANE's job).
+  if (o.fused_epilogue == 2) c->epi = EPI_SLAB;
+  else if (S == 1 && variant != NBX_KERNEL_SGPRW) c->epi = EPI_ROW;
+  else c->epi = EPI_SLAB;
+  c->grid_x = ceil_div(in.i_count, iblk); c->grid_y = S;
+}
+
+// nbx_create's launch plan: auto_shape, then the inner loop and graph replay.  NBX_OK, or NBX_ERR_ARG with the text of
+// nbx_last_error() in *msg.
+inline int plan_launch(const PlanInput& in, const nbx_opts& o, Plan* p, const char** msg) {
+  auto fail = [msg](const char* text) { *msg = text; return NBX_ERR_ARG; };
+  const int cus = in.cus > 0 ? in.cus : 256;
+  *p = Plan{};
+  auto_shape(p, in, o);
+  if (o.inner_loop != NBX_LOOP_AUTO && o.inner_loop != NBX_LOOP_CXX && o.inner_loop != NBX_LOOP_ASM && o.inner_loop != NBX_LOOP_ASM_TS &&
+      o.inner_loop != NBX_LOOP_ASM_PF)
+    return fail("nbx_create: inner_loop must be NBX_LOOP_AUTO, NBX_LOOP_CXX, NBX_LOOP_ASM, NBX_LOOP_ASM_TS or NBX_LOOP_ASM_PF");
+  // the hand-scheduled loop: where an instance with it is compiled and every wave's j range is whole trips of it (a quarter of a
+  // split under the wave split: 256-record splits)
+  const bool asm_loop_compiled = instance_index(plan_instance(*p, in.precision, false, LOOP_ASM)) >= 0 &&
+                                 (p->variant == NBX_KERNEL_JLANE || p->jps % kSgprGran == 0);
+  p->loop = (o.inner_loop != NBX_LOOP_CXX && asm_loop_compiled) ? LOOP_ASM : LOOP_CXX;
+  if ((o.inner_loop == NBX_LOOP_ASM || o.inner_loop == NBX_LOOP_ASM_TS || o.inner_loop == NBX_LOOP_ASM_PF) && p->loop != LOOP_ASM)
+    return fail("nbx_create: no hand-scheduled loop for this shape (needs fp32; kernel_variant SGPR with 1, 2 or 4 bodies per lane, SGPRW with j_per_split a multiple of 256 and 2 or 4 bodies per lane, or JLANE with 2, 4 or 8 bodies per wave)");
+  // Time-sliced wave priority (LOOP_ASM_TS) exists for the row-epilogue SGPR kernel: one workgroup row, every wave resident
+  // from the first cycle to the last.  Auto takes it when the fullest CU holds exactly two workgroups, i.e. two waves per
+  // SIMD: measured +4.5 % at 512 workgroups, +2.7 % at 384, -0.6 % with one wave per SIMD (nobody to alternate with, six
+  // more scalar instructions per trip) and -0.6 ... +0.3 % with three, four or eight (profiles/r02_time_sliced_ab.txt).
+  {
+    const bool ts_shape = p->loop == LOOP_ASM && p->variant == NBX_KERNEL_SGPR && p->epi == EPI_ROW && p->B >= 2;
+    if (o.inner_loop == NBX_LOOP_ASM_TS && !ts_shape)
+      return fail("nbx_create: NBX_LOOP_ASM_TS needs the single-row SGPR kernel (reference summation order or j_split 1, fp32, 2 or 4 bodies per lane)");
+    const bool two_per_simd = p->grid_x > cus && p->grid_x <= 2 * cus;
+    if (ts_shape && (o.inner_loop == NBX_LOOP_ASM_TS || (o.inner_loop == NBX_LOOP_AUTO && two_per_simd))) p->loop = LOOP_ASM_TS;
+    // L2 prefetch (LOOP_ASM_PF): the same kernels when the launch leaves one wave per SIMD -- a rank that owns 131072 of 1M bodies:
+    // +3.5 %; with two or more waves per SIMD the other waves are the cover and it costs 0.4-1.4 % (profiles/r04_b2_prefetch_ab.txt)
+    if (o.inner_loop == NBX_LOOP_ASM_PF && !ts_shape)
+      return fail("nbx_create: NBX_LOOP_ASM_PF needs the single-row SGPR kernel (reference summation order or j_split 1, fp32, 2 or 4 bodies per lane)");
+    if (ts_shape && (o.inner_loop == NBX_LOOP_ASM_PF || (o.inner_loop == NBX_LOOP_AUTO && p->grid_x <= cus))) p->loop = LOOP_ASM_PF;
+  }
+  // The jlane kernel's generated loop keeps four records per set in flight; with few bodies per wave that is too little
+  // arithmetic to cover an L2 round trip when a SIMD holds a single wave, and the compiled loop (eight records per set) is
+  // 3-4 % ahead there (profiles/r02_jlane_ab.txt).  Auto takes the generated loop where it measured faster: 8 bodies per wave,
+  // or 4 with more than one wave per SIMD.
+  if (o.inner_loop == NBX_LOOP_AUTO && p->variant == NBX_KERNEL_JLANE && p->loop == LOOP_ASM) {
+    const bool several_waves = ceil_div(in.i_count, p->B) > cus * 4;
+    if (!(p->B == 8 || (p->B == 4 && several_waves))) p->loop = LOOP_CXX;
+  }
+  // use_graph: 0 auto (launch-bound sizes only: < ~0.3 ms of pair work per step), 1 on, 2 off;
+  // capture needs a stream of our own
+  p->use_graph = in.own_stream && (o.use_graph == 1 || (o.use_graph == 0 && (double)in.i_count * (double)in.n < 1.5e9));
+  p->pairs = p->loop == LOOP_ASM && p->B == 1;  // sgpr_loop_asm_jpair
+  p->step = plan_instance(*p, in.precision, false, p->loop);
+  p->accel = plan_instance(*p, in.precision, true, p->loop);
+  return NBX_OK;
+}
+
+}  // namespace nbx

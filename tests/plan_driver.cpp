@@ -1,0 +1,90 @@
+// Host-only driver of the launch planner (nbody-demo-2023_amd/csrc/nbx_plan.hpp) for tests/test_launch_plan.py; g++, no ROCm.
+//   plan_driver rows CUS       stdin: "n precision i_begin i_count n_alloc bodies_per_lane j_split kernel_variant fused_epilogue
+//                              use_graph external_stream summation_order inner_loop cost" per line; stdout per row:
+//                              "P <plan fields>[ <force_cost at each own>]" or "E <rc> <message>"
+//   plan_driver cross CUS      every combination of the nbx_opts shape fields (out-of-range values included) at a handful of
+//                              sizes and slices, both precisions: exit 1 at the first plan whose step or accel kernel is not compiled
+//   plan_driver instances      the declared instance set, one "kind precision B jsrc epi math ws loop" per line
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "nbx_plan.hpp"
+
+using namespace nbx;
+
+static const int kOwns[] = {1, 255, 256, 257, 4096, 16384, 32768, 65535, 65536, 65537, 98304, 131072, 131073, 196608, 262144, 262145,
+                            393216, 524288, 524289, 786432, 1048576};
+
+// what nbx_create resolves before it plans: the owned count of a whole run and the tile-rounded record array
+static int plan(int n, int precision, int cus, const nbx_opts& o, Plan* p, const char** msg) {
+  const int i_count = o.i_count == 0 ? n - o.i_begin : o.i_count;
+  const int n_alloc = round_up(std::max(n, o.n_alloc), kTile);
+  return plan_launch({n, n_alloc, i_count, precision, cus, o.external_stream == 0}, o, p, msg);
+}
+
+static void print_instance(const Instance& k) {
+  std::printf("%d %d %d %d %d %d %d %d", k.kind, k.precision, k.B, k.jsrc, k.epi, k.math, k.ws ? 1 : 0, k.loop);
+}
+
+int main(int argc, char** argv) {
+  const char* mode = argc > 1 ? argv[1] : "";
+  const int cus = argc > 2 ? std::atoi(argv[2]) : 256;
+  if (!std::strcmp(mode, "instances")) {
+    for (const Instance& k : kInstances) { print_instance(k); std::printf("\n"); }
+    return 0;
+  }
+  if (!std::strcmp(mode, "rows")) {
+    int v[14];
+    while (std::scanf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8], &v[9],
+                      &v[10], &v[11], &v[12], &v[13]) == 14) {
+      nbx_opts o{};
+      o.i_begin = v[2]; o.i_count = v[3]; o.n_alloc = v[4]; o.bodies_per_lane = v[5]; o.j_split = v[6]; o.kernel_variant = v[7];
+      o.fused_epilogue = v[8]; o.use_graph = v[9]; o.external_stream = v[10]; o.summation_order = v[11]; o.inner_loop = v[12];
+      Plan p;
+      const char* msg = "";
+      const int rc = plan(v[0], v[1], cus, o, &p, &msg);
+      if (rc != NBX_OK) { std::printf("E %d %s\n", rc, msg); continue; }
+      std::printf("P %d %d %d %d %d %d %d %d %d %d %d %d", p.variant, p.order, p.B, p.S, p.jps, p.math, p.epi, p.loop, p.grid_x, p.grid_y,
+                  p.use_graph ? 1 : 0, p.pairs ? 1 : 0);
+      if (v[13])
+        for (int own : kOwns) std::printf(" %.17g", force_cost(p, v[1], cus, own));
+      std::printf("\n");
+    }
+    return 0;
+  }
+  if (!std::strcmp(mode, "cross")) {
+    struct Slice { int n, i_begin, i_count, n_alloc; };
+    const Slice slices[] = {{2048, 0, 0, 0}, {4099, 0, 0, 0}, {12288, 0, 0, 0}, {16384, 0, 0, 0}, {50000, 0, 0, 0}, {65536, 0, 0, 0},
+                            {262144, 0, 0, 0}, {1048576, 0, 0, 0}, {262144, 65536, 131072, 0}, {1048576, 917504, 131072, 0},
+                            {50000, 37632, 12368, 50176}};
+    const int bpl[] = {-1, 0, 1, 2, 3, 4, 8, 16, 32}, js[] = {-1, 0, 1, 2, 3, 7, 8, 32, 64, 1000}, kv[] = {-1, 0, 1, 2, 3, 4, 5, 6, 7},
+              fe[] = {-1, 0, 1, 2, 3}, ug[] = {-1, 0, 1, 2, 3}, es[] = {0, 1}, so[] = {-1, 0, 1, 2, 3}, il[] = {-1, 0, 1, 2, 3, 4, 5};
+    long plans = 0, errors = 0;
+    for (const Slice& s : slices)
+      for (int precision : {32, 64})
+        for (int a : bpl) for (int b : js) for (int c : kv) for (int d : fe) for (int e : ug) for (int f : es) for (int g : so) for (int h : il) {
+          nbx_opts o{};
+          o.i_begin = s.i_begin; o.i_count = s.i_count; o.n_alloc = s.n_alloc;
+          o.bodies_per_lane = a; o.j_split = b; o.kernel_variant = c; o.fused_epilogue = d; o.use_graph = e; o.external_stream = f;
+          o.summation_order = g; o.inner_loop = h;
+          Plan p;
+          const char* msg = "";
+          if (plan(s.n, precision, cus, o, &p, &msg) != NBX_OK) { ++errors; continue; }
+          ++plans;
+          if (instance_index(p.step) < 0 || instance_index(p.accel) < 0) {
+            std::printf("no instance: n %d i_begin %d i_count %d precision %d opts %d %d %d %d %d %d %d %d -> step ", s.n, s.i_begin, s.i_count,
+                        precision, a, b, c, d, e, f, g, h);
+            print_instance(p.step);
+            std::printf(", accel ");
+            print_instance(p.accel);
+            std::printf("\n");
+            return 1;
+          }
+        }
+    std::printf("%ld plans %ld errors\n", plans, errors);
+    return 0;
+  }
+  std::fprintf(stderr, "usage: plan_driver rows|cross|instances [cus]\n");
+  return 2;
+}

@@ -50,9 +50,34 @@ def _sregs(operand_text):
     return regs
 
 
-def test_every_force_kernel_instance_is_present(kernels):
-    names = [k for k in kernels if "force_kernel" in k]
-    assert len(names) >= 36, len(names)
+def _instance_key(name):
+    """(kind, precision, B, jsrc, epi, math, ws, loop) of a force-kernel symbol, as nbx_plan.hpp's kInstances spells it."""
+    prec = {"f": 32, "d": 64}
+    m = re.search(r"12force_kernelI([fd])Li(\d+)ELi(\d)ELi(\d)ELi1ELi(\d)ELb([01])ELi(\d)E", name)
+    if m:
+        return (0, prec[m.group(1)]) + tuple(int(x) for x in m.groups()[1:])
+    m = re.search(r"18force_jlane_kernelILi(\d+)ELi\d+ELi(\d)E", name)
+    if m:
+        return (1, 32, int(m.group(1)), 0, 0, 0, 0, int(m.group(2)))
+    m = re.search(r"22force_jlane_kernel_f64ILi(\d+)ELi\d+E", name)
+    if m:
+        return (1, 64, int(m.group(1)), 0, 0, 0, 0, 0)
+    m = re.search(r"18force_exact_kernelI([fd])Lb([01])E", name)
+    if m:
+        return (2, prec[m.group(1)], int(m.group(2)), 0, 0, 0, 0, 0)
+    return None
+
+
+def test_every_force_kernel_instance_is_present(kernels, tmp_path):
+    """The compiled force kernels are exactly the declared instance set (csrc/nbx_plan.hpp: kInstances)."""
+    from test_launch_plan import CSRC, DRIVER, declared_instances
+    exe = str(tmp_path / "plan_driver")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I", CSRC, DRIVER, "-o", exe])
+    declared = declared_instances(exe)
+    names = [k for k in kernels if re.search(r"force_(jlane_|exact_)?kernel", k)]
+    assert len(names) == len(declared), (len(names), len(declared))
+    assert sorted(_instance_key(k) for k in names) == sorted(declared)
+    assert sum("force_kernel" in k for k in kernels) == sum(k[0] == 0 for k in declared)
     assert any("integrate_kernel" in k for k in kernels) and any("ke_reduce_kernel" in k for k in kernels)
 
 

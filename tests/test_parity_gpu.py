@@ -307,7 +307,7 @@ def test_kenergy_trace_config1_n16384_s500(nbx, variant):
 def test_config1_launch_shape_is_frozen(nbx):
     """VERDICT r2 item 4a.  configs[1] runs 450 steps past the bounce; which side of 1e-4 a late printed row lands on depends
     on the summation tree (profiles/r02_config1_by_kernel.txt: SGPRW 7.7e-5, LDS 8.5e-5, jlane 1.7e-4 at the same step).  The
-    shape that passes is therefore part of the contract for n = 16384: a retune of auto_shape that changes ANY of these must
+    shape that passes is therefore part of the contract for n = 16384: a retune of csrc/nbx_plan.hpp that changes ANY of these must
     come with test_kenergy_trace_config1_n16384_s500 still green -- this test makes such a change visible instead of silent."""
     with nbx.Context(16384) as c:
         st = c.stats()
@@ -321,7 +321,7 @@ def test_config1_launch_shape_is_frozen(nbx):
                                         (50000, 32, 196), (65536, 2, 256), (98304, 2, 384), (131072, 1, 512)])
 def test_balanced_j_split_rule(nbx, n, S, grid_x):
     """Round 3: tree-order shapes above 16384 owned bodies take the j-split that loads every CU evenly with
-    the fewest slabs (csrc/nbx_api.hip: balanced_j_split; measured in profiles/r03_band_sweep.txt), in whole 256-record tiles so
+    the fewest slabs (csrc/nbx_plan.hpp: balanced_j_split; measured in profiles/r03_band_sweep.txt), in whole 256-record tiles so
     that the hand-scheduled loop serves every n; up to 16384 the round-1 rule stays (configs[1]'s tree is pinned)."""
     with nbx.Context(n) as c:
         st = c.stats()
