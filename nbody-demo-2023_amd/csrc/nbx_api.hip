@@ -66,10 +66,10 @@ void launch_instance(nbx_ctx* c, double dt, int acc_only) {
                        (const T*)c->mass_all, (T4*)c->accp, c->i_begin, c->i_count, c->n);
   else if constexpr (k.kind == INST_FORCE)
     hipLaunchKernelGGL((force_kernel<T, k.B, k.jsrc, k.epi, 1, k.math, k.ws, k.loop>), grid, dim3(kBlock), 0, c->stream, force_args<T>(c, dt));
-  else if constexpr (k.precision == 32)  // D = prefetch depth of the compiled loop / tail; the generated loop exists for NB <= 8
-    hipLaunchKernelGGL((force_jlane_kernel<k.B, (k.B <= 4 ? 8 : 4), k.loop>), grid, dim3(kBlock), 0, c->stream, force_args<T>(c, dt), acc_only);
+  else if constexpr (k.precision == 32)  // jlane_depth: prefetch depth of the compiled loop / tail (nbx_plan.hpp)
+    hipLaunchKernelGGL((force_jlane_kernel<k.B, jlane_depth(32, k.B), k.loop>), grid, dim3(kBlock), 0, c->stream, force_args<T>(c, dt), acc_only);
   else
-    hipLaunchKernelGGL((force_jlane_kernel_f64<k.B, (k.B == 2 ? 8 : 4)>), grid, dim3(kBlock), 0, c->stream, force_args<T>(c, dt), acc_only);
+    hipLaunchKernelGGL((force_jlane_kernel_f64<k.B, jlane_depth(64, k.B)>), grid, dim3(kBlock), 0, c->stream, force_args<T>(c, dt), acc_only);
 }
 
 template <int... I>

@@ -21,6 +21,10 @@ constexpr int kBlock = 256;  // threads per workgroup
 constexpr int kTile = 256;   // j records per LDS tile (BASELINE.json configs[1]: "LDS j-tile=256")
 // j-range granule of the plain SGPR kernel: whole trips of every hand-scheduled loop (nbx_api.hip checks it against kSgprAsmTrip<>)
 constexpr int kSgprGran = 256;
+// spare records behind posm[n_alloc), zero-filled: the pipelined scalar loop requests one batch (16 records at most) past
+// the end, the jlane kernel one trip of its widest prefetch (8 blocks of 64 records); nothing read there is ever applied
+// (here and not with the kernels: plan_ensemble bounds the record index of an ensemble, whose members each carry the spare records)
+constexpr int kSgprOverread = 16 + 8 * 64;
 
 enum : int { JSRC_LDS = 1, JSRC_SGPR = 2 };
 enum : int { MATH_SCALAR = 0, MATH_PACKED = 1 };
@@ -204,6 +208,42 @@ inline int balanced_j_split(int bi, int cus, int max_s) {
   return pick ? pick : largest;
 }
 
+// Bodies per wave of the one-launch kernel (force_jlane_kernel; ensemble_step_kernel with `members` systems of `own` bodies in one
+// launch).  A launch lasts as long as the fullest SIMD: ceil(waves / SIMDs) rounds of NB bodies each, times what a body-round costs
+// with that NB; the waves of all members count, each member having ceil(own / NB) of its own.  Measured per body-round and per j
+// record, relative to NB = 8 (profiles/r03_jlane_band.txt: the same ratios at 12288, 13000 and 16383 bodies): 2 bodies per wave 1.29
+// (every wave streams all j records and transposes through LDS for two bodies only), 4 -> 1.06, 8 -> 1.00 (the generated loop),
+// 16 -> 1.06 (compiled loop only).  Smallest product wins, ties to the larger NB.  One system: 2048 -> 2, 4096 -> 4, 8192 -> 8,
+// 12288 -> 4 (three full rounds), 13000 ... 16383 -> 8 -- the measured optimum at each.  Round 2 counted body-rounds alone, which
+// sent 13000 and 14336 to NB = 2 (56.6 us against 50.1 with 8).
+// fp64 (no generated loop, other ratios not measured): body-rounds alone, ties to the larger NB, as in round 2.
+// Ensembles (members > 1; profiles/ensemble_sweep.json, which records the time of every NB next to the one taken here): where 16
+// bodies per wave still give every SIMD a wave, they beat 8 at every cell measured -- 0.92 of its time at n = 2048 x 16 members,
+// 0.95 at 2048 x 64, 0.97-0.98 at 4096 x 4 / 16 / 64, 0.98-0.99 at 8192 x 4 / 16 / 64: a wave's fixed cost (64 LDS reads per body column,
+// the epilogue) is spread over twice the bodies and half as many waves stream a member's j records, which weighs most where the j
+// loop is short -- so their weight there is 0.97.  With fewer waves than SIMDs 16 lose as the table says (2048 x 4: 1.41 of 8's
+// time), and a lone system keeps the table it was measured with (16383 bodies: 8 per wave).
+inline int jlane_bodies_per_wave(int own, int members, int precision, int cus, int max_nb = 16) {
+  max_nb = std::min(max_nb, precision == 32 ? 16 : 8);  // fp64 bodies take two SGPRs per coordinate
+  int NB = 2;
+  long long best = 0;
+  for (int nb = 2; nb <= max_nb; nb *= 2) {
+    const long long waves = (long long)members * ceil_div(own, nb), simds = (long long)cus * 4;
+    long long weight = precision != 32 ? 100 : (nb == 2 ? 129 : nb == 8 ? 100 : 106);
+    if (precision == 32 && nb == 16 && members > 1 && waves >= simds) weight = 97;
+    const long long cost = ((waves + simds - 1) / simds) * nb * weight;
+    if (best == 0 || cost <= best) { best = cost; NB = nb; }
+  }
+  return NB;
+}
+// NBX_LOOP_AUTO, jlane kernel with a generated loop for its NB: the generated loop keeps four records per set in flight; with few
+// bodies per wave that is too little arithmetic to cover an L2 round trip when a SIMD holds a single wave, and the compiled loop
+// (eight records per set) is 3-4 % ahead there (profiles/r02_jlane_ab.txt).  Auto takes the generated loop where it measured
+// faster: 8 bodies per wave, or 4 with more than one wave per SIMD.  `waves` = the launch's (all members of an ensemble).
+inline bool jlane_auto_takes_generated_loop(int NB, long long waves, int cus) { return NB == 8 || (NB == 4 && waves > (long long)cus * 4); }
+// prefetch depth D of the compiled loop / tail: records per register set (the generated loop exists for NB <= 8)
+constexpr int jlane_depth(int precision, int NB) { return precision == 32 ? (NB <= 4 ? 8 : 4) : (NB == 2 ? 8 : 4); }
+
 // What the shape rules read: the context as nbx_create resolved it (n_alloc rounded to the tile, i_count of a whole run = n), the
 // device's CU count (<= 0: taken as 256) and whether the context owns its stream (a caller's stream is not captured for replay).
 struct PlanInput { int n, n_alloc, i_count, precision, cus; bool own_stream; };
@@ -260,21 +300,7 @@ inline void auto_shape(Plan* c, const PlanInput& in, const nbx_opts& o) {
                           in.i_count <= (in.precision == 32 ? kJlaneMaxOwn : kJlaneMaxOwnF64);
   if (variant == NBX_KERNEL_JLANE || jlane_auto) {
     int NB = o.bodies_per_lane;
-    if ((NB != 2 && NB != 4 && NB != 8 && NB != 16) || NB > max_nb) {
-      // A launch lasts as long as the fullest SIMD: ceil(waves / SIMDs) rounds of NB bodies each, times what a body-round costs
-      // with that NB.  Measured per body-round and per j record, relative to NB = 8 (profiles/r03_jlane_band.txt: the same ratios
-      // at 12288, 13000 and 16383 bodies): 2 bodies per wave 1.29 (every wave streams all j records and transposes through LDS
-      // for two bodies only), 4 -> 1.06, 8 -> 1.00 (the generated loop), 16 -> 1.06 (compiled loop only).  Smallest product wins:
-      // 2048 -> 2, 4096 -> 4, 8192 -> 8, 12288 -> 4 (three full rounds), 13000 ... 16383 -> 8 -- the measured optimum at each.
-      // Round 2 counted body-rounds alone, which sent 13000 and 14336 to NB = 2 (56.6 us against 50.1 with 8).
-      // fp64 (no generated loop, other ratios not measured): body-rounds alone, ties to the larger NB, as in round 2.
-      long best = 0;
-      for (int nb = 2; nb <= max_nb; nb *= 2) {
-        const long weight = in.precision != 32 ? 100 : (nb == 2 ? 129 : nb == 8 ? 100 : 106);
-        const long cost = (long)ceil_div(ceil_div(in.i_count, nb), cus * 4) * nb * weight;
-        if (best == 0 || cost <= best) { best = cost; NB = nb; }
-      }
-    }
+    if ((NB != 2 && NB != 4 && NB != 8 && NB != 16) || NB > max_nb) NB = jlane_bodies_per_wave(in.i_count, 1, in.precision, cus);
     c->B = NB; c->S = 1; c->jps = in.n_alloc; c->math = in.precision == 32 ? MATH_PACKED : MATH_SCALAR; c->variant = NBX_KERNEL_JLANE; c->epi = EPI_ROW;
     c->grid_x = ceil_div(ceil_div(in.i_count, NB), 4); c->grid_y = 1;
     return;
@@ -354,20 +380,93 @@ inline int plan_launch(const PlanInput& in, const nbx_opts& o, Plan* p, const ch
       return fail("nbx_create: NBX_LOOP_ASM_PF needs the single-row SGPR kernel (reference summation order or j_split 1, fp32, 2 or 4 bodies per lane)");
     if (ts_shape && (o.inner_loop == NBX_LOOP_ASM_PF || (o.inner_loop == NBX_LOOP_AUTO && p->grid_x <= cus))) p->loop = LOOP_ASM_PF;
   }
-  // The jlane kernel's generated loop keeps four records per set in flight; with few bodies per wave that is too little
-  // arithmetic to cover an L2 round trip when a SIMD holds a single wave, and the compiled loop (eight records per set) is
-  // 3-4 % ahead there (profiles/r02_jlane_ab.txt).  Auto takes the generated loop where it measured faster: 8 bodies per wave,
-  // or 4 with more than one wave per SIMD.
-  if (o.inner_loop == NBX_LOOP_AUTO && p->variant == NBX_KERNEL_JLANE && p->loop == LOOP_ASM) {
-    const bool several_waves = ceil_div(in.i_count, p->B) > cus * 4;
-    if (!(p->B == 8 || (p->B == 4 && several_waves))) p->loop = LOOP_CXX;
-  }
+  if (o.inner_loop == NBX_LOOP_AUTO && p->variant == NBX_KERNEL_JLANE && p->loop == LOOP_ASM &&
+      !jlane_auto_takes_generated_loop(p->B, ceil_div(in.i_count, p->B), cus))
+    p->loop = LOOP_CXX;
   // use_graph: 0 auto (launch-bound sizes only: < ~0.3 ms of pair work per step), 1 on, 2 off;
   // capture needs a stream of our own
   p->use_graph = in.own_stream && (o.use_graph == 1 || (o.use_graph == 0 && (double)in.i_count * (double)in.n < 1.5e9));
   p->pairs = p->loop == LOOP_ASM && p->B == 1;  // sgpr_loop_asm_jpair
   p->step = plan_instance(*p, in.precision, false, p->loop);
   p->accel = plan_instance(*p, in.precision, true, p->loop);
+  return NBX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Ensembles (include/nbx_ensemble.h): `members` independent systems of n bodies advanced by one launch per step, grid
+// (workgroups per member, members).  Every member runs the jlane kernel body exactly as a context of that NB and loop does.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace instance_list {  // the ensemble_step_kernel instances nbx_ensemble.hip compiles: the jlane rows of kInstances
+constexpr Instance kEnsembleInstances[] = {
+    {J, 32, 2, 0, 0, 0, false, ASM}, {J, 32, 2, 0, 0, 0, false, CXX}, {J, 32, 4, 0, 0, 0, false, ASM}, {J, 32, 4, 0, 0, 0, false, CXX},
+    {J, 32, 8, 0, 0, 0, false, ASM}, {J, 32, 8, 0, 0, 0, false, CXX}, {J, 32, 16, 0, 0, 0, false, CXX},
+    {J, 64, 2, 0, 0, 0, false, CXX}, {J, 64, 4, 0, 0, 0, false, CXX}, {J, 64, 8, 0, 0, 0, false, CXX},
+};
+}  // namespace instance_list
+using instance_list::kEnsembleInstances;
+constexpr int kEnsembleInstanceCount = (int)(sizeof(kEnsembleInstances) / sizeof(kEnsembleInstances[0]));
+constexpr int ensemble_instance_index(const Instance& k) {
+  for (int i = 0; i < kEnsembleInstanceCount; ++i)
+    if (kEnsembleInstances[i] == k) return i;
+  return -1;
+}
+constexpr bool ensemble_instances_mirror_the_jlane_rows() {
+  int rows = 0;
+  for (int i = 0; i < kInstanceCount; ++i)
+    if (kInstances[i].kind == INST_JLANE) { ++rows; if (ensemble_instance_index(kInstances[i]) < 0) return false; }
+  return rows == kEnsembleInstanceCount;
+}
+static_assert(ensemble_instances_mirror_the_jlane_rows(), "a member must be able to run every shape a jlane context can, and no other");
+
+constexpr int kEnsembleMaxMembers = 65535;  // gridDim.y
+
+struct EnsemblePlan {
+  int n_alloc = 0;        // records per member (n rounded up to the tile), followed by kSgprOverread spare records
+  int NB = 0, loop = LOOP_CXX, D = 0;
+  int grid_x = 0, grid_y = 0;  // workgroups per member (what a context of this NB launches), members
+  Instance step{};
+};
+
+// nbx_ensemble_create's plan.  NBX_OK, or NBX_ERR_ARG with the text of nbx_last_error() in *msg.  Reads of `o`: bodies_per_lane,
+// inner_loop and the fields an ensemble cannot honour (which must be at their defaults).
+inline int plan_ensemble(int n, int precision, int members, int cus, const nbx_opts& o, EnsemblePlan* p, const char** msg) {
+  auto fail = [msg](const char* text) { *msg = text; return NBX_ERR_ARG; };
+  *p = EnsemblePlan{};
+  if (cus <= 0) cus = 256;
+  if (precision != 32 && precision != 64) return fail("nbx_ensemble_create: precision must be 32 or 64");
+  if (n < 1) return fail("nbx_ensemble_create: n must be > 0");
+  if (n > (precision == 32 ? kJlaneMaxOwn : kJlaneMaxOwnF64))
+    return fail("nbx_ensemble_create: n is beyond the one-launch kernel's range (fp32: 16383, fp64: 12288 bodies); a system of that size fills the card on its own: use nbx_create");
+  if (members < 1 || members > kEnsembleMaxMembers) return fail("nbx_ensemble_create: members must be in [1, 65535] (one grid row per member)");
+  const int n_alloc = round_up(n, kTile);
+  // (cannot be reached with today's limits -- 65535 x (16384 + 528) records; it is what the host's int offsets rest on if they move)
+  if ((long long)members * (n_alloc + kSgprOverread) > 0x7fffffffLL)
+    return fail("nbx_ensemble_create: members x (records per member + spare records) must fit 31 bits of record index");
+  if (o.kernel_variant != NBX_KERNEL_AUTO && o.kernel_variant != NBX_KERNEL_JLANE)
+    return fail("nbx_ensemble_create: kernel_variant must be NBX_KERNEL_AUTO or NBX_KERNEL_JLANE (an ensemble steps with the one-launch kernel body)");
+  if (o.summation_order != NBX_ORDER_AUTO && o.summation_order != NBX_ORDER_TREE)
+    return fail("nbx_ensemble_create: summation_order must be NBX_ORDER_AUTO or NBX_ORDER_TREE (the one-launch kernel sums in tree order)");
+  if (o.j_split > 1) return fail("nbx_ensemble_create: j_split must be 0 or 1 (a member's j range is not split over workgroups)");
+  if (o.i_begin != 0 || o.i_count != 0) return fail("nbx_ensemble_create: i_begin and i_count must be 0 (an ensemble is not sharded; run one ensemble per GPU)");
+  if (o.external_stream != 0) return fail("nbx_ensemble_create: external_stream must be 0 (an ensemble steps on a stream of its own)");
+  const int max_nb = precision == 32 ? 16 : 8;
+  int NB = o.bodies_per_lane;
+  if (NB != 0 && ((NB != 2 && NB != 4 && NB != 8 && NB != 16) || NB > max_nb))
+    return fail("nbx_ensemble_create: bodies_per_lane must be 0 (auto), 2, 4, 8 or -- fp32 only -- 16 bodies per wave");
+  if (o.inner_loop != NBX_LOOP_AUTO && o.inner_loop != NBX_LOOP_CXX && o.inner_loop != NBX_LOOP_ASM)
+    return fail("nbx_ensemble_create: inner_loop must be NBX_LOOP_AUTO, NBX_LOOP_CXX or NBX_LOOP_ASM");
+  // the hand-scheduled loop asked for by name: the choice is among the shapes that have one (fp32: up to 8 bodies per wave)
+  if (NB == 0) NB = jlane_bodies_per_wave(n, members, precision, cus, o.inner_loop == NBX_LOOP_ASM && precision == 32 ? 8 : 16);
+  const bool asm_loop_compiled = ensemble_instance_index({INST_JLANE, precision, NB, 0, 0, 0, false, LOOP_ASM}) >= 0;
+  int loop = (o.inner_loop != NBX_LOOP_CXX && asm_loop_compiled) ? LOOP_ASM : LOOP_CXX;
+  if (o.inner_loop == NBX_LOOP_ASM && loop != LOOP_ASM)
+    return fail("nbx_ensemble_create: no hand-scheduled loop for this shape (needs fp32 and 2, 4 or 8 bodies per wave)");
+  if (o.inner_loop == NBX_LOOP_AUTO && loop == LOOP_ASM && !jlane_auto_takes_generated_loop(NB, (long long)members * ceil_div(n, NB), cus))
+    loop = LOOP_CXX;
+  p->n_alloc = n_alloc;
+  p->NB = NB; p->loop = loop; p->D = jlane_depth(precision, NB);
+  p->grid_x = ceil_div(ceil_div(n, NB), 4); p->grid_y = members;
+  p->step = {INST_JLANE, precision, NB, 0, 0, 0, false, loop};
   return NBX_OK;
 }
 

@@ -31,6 +31,12 @@ SYMBOLS = (
 # the symbols of include/nbx_diag.h (physics diagnostics), kept apart from the set nbx.h declares
 DIAG_SYMBOLS = ("nbx_diagnostics", "nbx_group_diagnostics")
 
+# the symbols of include/nbx_ensemble.h (many small systems per launch), kept apart likewise
+ENSEMBLE_SYMBOLS = (
+    "nbx_ensemble_create", "nbx_ensemble_destroy", "nbx_ensemble_upload", "nbx_ensemble_step", "nbx_ensemble_step_trace",
+    "nbx_ensemble_download", "nbx_ensemble_sync", "nbx_ensemble_profile", "nbx_ensemble_stats",
+)
+
 
 class NbxError(RuntimeError):
     def __init__(self, code, where, text):
@@ -80,6 +86,19 @@ class Diag(ctypes.Structure):
         d["mass_moment"] = list(self.mass_moment)
         d["etotal"] = self.kenergy + self.potential
         return d
+
+
+class EnsembleStats(ctypes.Structure):
+    """nbx_ensemble_stats_t (include/nbx_ensemble.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("n", ctypes.c_int32), ("n_alloc", ctypes.c_int32), ("members", ctypes.c_int32),
+        ("precision", ctypes.c_int32), ("bodies_per_lane", ctypes.c_int32), ("inner_loop", ctypes.c_int32),
+        ("grid_x", ctypes.c_int32), ("grid_y", ctypes.c_int32), ("block", ctypes.c_int32), ("cu_count", ctypes.c_int32),
+        ("steps_done", ctypes.c_int64), ("launches_timed", ctypes.c_int64), ("step_ms_total", ctypes.c_double),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
 
 
 _lib = None
@@ -143,6 +162,17 @@ def load():
     L.nbx_group_retune.argtypes = [vp, pd, ctypes.POINTER(i32)]
     L.nbx_diagnostics.argtypes = [vp, ctypes.POINTER(Diag)]
     L.nbx_group_diagnostics.argtypes = [vp, ctypes.POINTER(Diag)]
+    if hasattr(L, "nbx_ensemble_create"):  # a library built without nbx_ensemble.hip still serves everything else
+        L.nbx_ensemble_create.argtypes = [ctypes.POINTER(vp), i32, i32, i32, ctypes.POINTER(Opts)]
+        L.nbx_ensemble_destroy.argtypes = [vp]
+        L.nbx_ensemble_destroy.restype = None
+        L.nbx_ensemble_upload.argtypes = [vp, i32, i32] + [vp] * 7
+        L.nbx_ensemble_step.argtypes = [vp, dbl, i32, vp]
+        L.nbx_ensemble_step_trace.argtypes = [vp, dbl, i32, vp]
+        L.nbx_ensemble_download.argtypes = [vp, i32, i32] + [vp] * 6
+        L.nbx_ensemble_sync.argtypes = [vp]
+        L.nbx_ensemble_profile.argtypes = [vp, i32]
+        L.nbx_ensemble_stats.argtypes = [vp, ctypes.POINTER(EnsembleStats)]
     _lib = L
     return L
 
@@ -281,6 +311,86 @@ class Context:
         d.struct_size = ctypes.sizeof(Diag)
         _check(self._L.nbx_diagnostics(self._h, ctypes.byref(d)), "nbx_diagnostics")
         return d.asdict()
+
+
+class Ensemble:
+    """One nbx_ensemble (include/nbx_ensemble.h): `members` independent systems of n bodies, one launch per time step for all
+    of them.  Keyword options are the nbx_opts fields an ensemble honours (device, bodies_per_lane, inner_loop)."""
+
+    def __init__(self, n, members, precision=32, **opts):
+        self._L = load()
+        if not hasattr(self._L, "nbx_ensemble_create"):
+            raise NbxError(NBX_ERR_STATE, "nbx_ensemble_create", "%s was built without the ensemble entry points" % LIB_PATH)
+        self._h = ctypes.c_void_p()
+        self.n, self.members, self.precision = int(n), int(members), int(precision)
+        o = Opts()
+        o.struct_size = ctypes.sizeof(Opts)
+        o.device = -1
+        for k, v in opts.items():
+            if not hasattr(o, k):
+                raise TypeError("unknown nbx_opts field %r" % k)
+            setattr(o, k, v)
+        _check(self._L.nbx_ensemble_create(ctypes.byref(self._h), self.n, self.precision, self.members, ctypes.byref(o)),
+               "nbx_ensemble_create")
+        self.dtype = _dtype(self.precision)
+
+    def close(self):
+        if self._h:
+            self._L.nbx_ensemble_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def upload(self, states, first=0):
+        """Members first, first + 1, ...: a list of state dicts (what initial_conditions returns), or one dict of (count, n) arrays."""
+        if isinstance(states, dict):
+            arrs = [np.ascontiguousarray(states[f], dtype=self.dtype) for f in FIELDS]
+        else:
+            arrs = [np.ascontiguousarray(np.stack([np.asarray(s[f]) for s in states]), dtype=self.dtype) for f in FIELDS]
+        for a in arrs:
+            if a.ndim != 2 or a.shape != (arrs[0].shape[0], self.n):
+                raise NbxError(NBX_ERR_ARG, "array", "expected shape (count, %d), got %r" % (self.n, a.shape))
+        _check(self._L.nbx_ensemble_upload(self._h, first, arrs[0].shape[0], *[_ptr(a) for a in arrs]), "nbx_ensemble_upload")
+
+    def step(self, nsteps, dt=DT, kenergy=True):
+        """nsteps steps of every member; the kinetic energy of each member after the last one (array of `members`) if asked for."""
+        ke = np.zeros(self.members, dtype=np.float64) if kenergy else None
+        _check(self._L.nbx_ensemble_step(self._h, dt, nsteps, _ptr(ke)), "nbx_ensemble_step")
+        return ke
+
+    def step_trace(self, nsteps, dt=DT):
+        """The kinetic energy of every member after every step: array (nsteps, members)."""
+        ke = np.zeros((max(nsteps, 1), self.members), dtype=np.float64)
+        _check(self._L.nbx_ensemble_step_trace(self._h, dt, nsteps, _ptr(ke)), "nbx_ensemble_step_trace")
+        return ke[:nsteps]
+
+    def download(self, first=0, count=None):
+        count = self.members - first if count is None else count
+        out = {f: np.zeros((max(count, 0), self.n), dtype=self.dtype) for f in FIELDS[:6]}
+        _check(self._L.nbx_ensemble_download(self._h, first, count, *[_ptr(out[f]) for f in FIELDS[:6]]), "nbx_ensemble_download")
+        return out
+
+    def sync(self):
+        _check(self._L.nbx_ensemble_sync(self._h), "nbx_ensemble_sync")
+
+    def profile(self, enable=True):
+        _check(self._L.nbx_ensemble_profile(self._h, 1 if enable else 0), "nbx_ensemble_profile")
+
+    def stats(self):
+        s = EnsembleStats()
+        s.struct_size = ctypes.sizeof(EnsembleStats)
+        _check(self._L.nbx_ensemble_stats(self._h, ctypes.byref(s)), "nbx_ensemble_stats")
+        return s.asdict()
 
 
 class Group:
