@@ -20,8 +20,9 @@ template <typename T> __host__ __device__ constexpr T grav_const() { return (T)6
 // c/sqrt(x) with c = rsq_scale<T>().  fp32: the raw v_rsq_f32, c = 1 (<= 1 ulp; r2 >= 1e-3 so no
 // denormal/zero handling is needed -- the ocml rsqrtf wrapper would add scaling code per pair).
 // fp64: v_rsq_f64 is a ~2^-26 seed (measured 1.2e-8 on the accelerations); ONE Newton step
-// y' = y/2 * (3 - x*y*y) takes it to ~3e-16 (measured 4.6e-15 on accelerations, 2.8e-15 on a
-// 500-step kenergy trace; the gate is 1e-10).  The step's factor 1/2 is not applied here: the
+// y' = y/2 * (3 - x*y*y) takes it to 3/2 e^2 of the seed's error e (measured 4.6e-15 on accelerations, 2.8e-15 on a
+// 500-step kenergy trace; the potential of nbx_diag uses it, the pair term has gm_inv_cube below).  The step's factor
+// 1/2 is not applied here: the
 // function returns 2/sqrt(x) and the records carry G*m/8 instead (exact power-of-two scaling,
 // gm_prescale<double>()), which saves one multiply per pair: 3 VALU for the step instead of 4.
 template <typename T> __host__ __device__ constexpr T gm_prescale() { return sizeof(T) == 8 ? (T)0.125 : (T)1; }
@@ -33,19 +34,37 @@ __device__ __forceinline__ double rsq(double x) {
   return y * u;
 }
 
+// gmj * r2^-3/2 with gmj the record's .w (G*m_j * gm_prescale<T>()).  fp32: (gmj * inv) * inv^2 with the raw v_rsq_f32.
+// fp64: the Newton step of rsq() above leaves 3/2 e^2 of the seed's error e on 1/sqrt, three times that on the cube -- and e
+// reaches 2^-25 at some arguments, i.e. up to 40 units of 2^-53 on a pair term (tests/test_step_probe_gpu.py saw exactly that on
+// bodies whose acceleration is one dominant term).  So the cube is corrected directly, to second order in the seed's residual
+// h = 1 - x y^2 = 1 - (1 + e)^2:  x^-3/2 = y^3 (1 - h)^-3/2 = y^3 (1 + 3/2 h + 15/8 h^2 + O(h^3)), h^3 < 2^-70.  y^2 serves both
+// the residual and the cube, the x8 of the prescale is folded into the polynomial: 7 VALU where the Newton form took 6, and
+// about 5 units of rounding whatever the seed does.
+__device__ __forceinline__ float gm_inv_cube(float gmj, float r2) {
+  const float inv = rsq(r2);
+  const float inv2 = inv * inv;
+  return (gmj * inv) * inv2;
+}
+__device__ __forceinline__ double gm_inv_cube(double gmj, double r2) {
+  const double y = __builtin_amdgcn_rsq(r2);
+  const double y2 = y * y;
+  const double h = __builtin_fma(-r2, y2, 1.0);
+  const double q = __builtin_fma(h, __builtin_fma(h, 15.0, 12.0), 8.0);  // 8 (1 + 3/2 h + 15/8 h^2)
+  return ((gmj * y) * y2) * q;
+}
+
 __device__ __forceinline__ float fmaT(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fmaT(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
-// One pair: 3 sub, 3 FMA (r^2 + eps^2), 1 rsq, 3 mul (G*m_j * inv^3), 3 FMA (accumulate)
+// One pair: 3 sub, 3 FMA (r^2 + eps^2), 1 rsq, 3 mul (G*m_j * inv^3; fp64: 7, gm_inv_cube), 3 FMA (accumulate)
 // = 12 VALU + 1 transcendental = the 20 "algorithmic" flops of DESIGN.md.
-// gmj is the record's .w = G*m_j * gm_prescale<T>(), inv = rsq_scale * r2^-1/2 (see rsq above).
+// gmj is the record's .w = G*m_j * gm_prescale<T>().
 template <typename T>
 __device__ __forceinline__ void pair(T xj, T yj, T zj, T gmj, T xi, T yi, T zi, T& ax, T& ay, T& az) {
   const T dx = xj - xi, dy = yj - yi, dz = zj - zi;
   const T r2 = fmaT(dx, dx, fmaT(dy, dy, fmaT(dz, dz, softening2<T>())));
-  const T inv = rsq(r2);
-  const T inv2 = inv * inv;
-  const T s = (gmj * inv) * inv2;
+  const T s = gm_inv_cube(gmj, r2);
   ax = fmaT(dx, s, ax);
   ay = fmaT(dy, s, ay);
   az = fmaT(dz, s, az);

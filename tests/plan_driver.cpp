@@ -2,6 +2,8 @@
 //   plan_driver rows CUS       stdin: "n precision i_begin i_count n_alloc bodies_per_lane j_split kernel_variant fused_epilogue
 //                              use_graph external_stream summation_order inner_loop cost" per line; stdout per row:
 //                              "P <plan fields>[ <force_cost at each own>]" or "E <rc> <message>"
+//   plan_driver both CUS       the same rows on stdin; stdout per row: "P <plan fields> <step instance> <accel instance>" (the two kernel
+//                              instances of the plan as `instances` prints them) or "E <rc> <message>"
 //   plan_driver cross CUS      every combination of the nbx_opts shape fields (out-of-range values included) at a handful of
 //                              sizes and slices, both precisions: exit 1 at the first plan whose step or accel kernel is not compiled
 //   plan_driver instances      the declared instance set, one "kind precision B jsrc epi math ws loop" per line
@@ -34,7 +36,8 @@ int main(int argc, char** argv) {
     for (const Instance& k : kInstances) { print_instance(k); std::printf("\n"); }
     return 0;
   }
-  if (!std::strcmp(mode, "rows")) {
+  const bool both = !std::strcmp(mode, "both");
+  if (both || !std::strcmp(mode, "rows")) {
     int v[14];
     while (std::scanf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8], &v[9],
                       &v[10], &v[11], &v[12], &v[13]) == 14) {
@@ -47,7 +50,12 @@ int main(int argc, char** argv) {
       if (rc != NBX_OK) { std::printf("E %d %s\n", rc, msg); continue; }
       std::printf("P %d %d %d %d %d %d %d %d %d %d %d %d", p.variant, p.order, p.B, p.S, p.jps, p.math, p.epi, p.loop, p.grid_x, p.grid_y,
                   p.use_graph ? 1 : 0, p.pairs ? 1 : 0);
-      if (v[13])
+      if (both) {
+        std::printf(" ");
+        print_instance(p.step);
+        std::printf(" ");
+        print_instance(p.accel);
+      } else if (v[13])
         for (int own : kOwns) std::printf(" %.17g", force_cost(p, v[1], cus, own));
       std::printf("\n");
     }
@@ -85,6 +93,6 @@ int main(int argc, char** argv) {
     std::printf("%ld plans %ld errors\n", plans, errors);
     return 0;
   }
-  std::fprintf(stderr, "usage: plan_driver rows|cross|instances [cus]\n");
+  std::fprintf(stderr, "usage: plan_driver rows|both|cross|instances [cus]\n");
   return 2;
 }

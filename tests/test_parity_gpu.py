@@ -1575,9 +1575,13 @@ def test_auto_order_threshold(nbx):
         assert c.stats()["summation_order"] == nbx.ORDER_TREE
 
 
-def test_randomized_shapes_orders_and_sizes_against_exact_mode(nbx):
+def test_randomized_shapes_orders_and_sizes_against_exact_mode(nbx, oracle):
     """80 pseudo-random (n, precision, kernel, bodies/lane, j-split, order, epilogue, slice) combinations, fixed seed: every one
-    must agree with the bit-exact reference arithmetic on the accelerations (2e-5 of |a|inf) and on a 3-step state."""
+    must agree with the bit-exact reference arithmetic on the accelerations (2e-5 of |a|inf) and on a 3-step state.  The un-sliced
+    ones also take the zero-velocity probe of tests/test_step_probe_gpu.py: every body of the step kernel against a
+    high-precision direct sum, under the gate of tests/force_ref.py (the atol below lets a 1 % error of one body pass)."""
+    import force_ref
+    from test_step_probe_gpu import reference_of, state_of
     rng = np.random.default_rng(20261004)
     tried = 0
     for _ in range(80):
@@ -1611,6 +1615,13 @@ def test_randomized_shapes_orders_and_sizes_against_exact_mode(nbx):
                 d1, d2 = c.download(), x.download()
                 for f in d1:
                     assert np.allclose(d1[f], d2[f], rtol=1e-4 if prec == 32 else 1e-11, atol=1e-6 if prec == 32 else 1e-14), (n, opts, f)
+                tr, k_ref = reference_of(oracle, "seed42", n, prec)
+                c.upload(state_of(oracle, "seed42", n, prec))
+                c.step(1)
+                d1 = c.download()
+                K = force_ref.k_metric(force_ref.accel_from_v1(np.stack([d1["vel_x"], d1["vel_y"], d1["vel_z"]], axis=1), prec), tr, prec)
+                bad = np.flatnonzero(~(K <= force_ref.gate(k_ref.max())))
+                assert bad.size == 0, (n, prec, opts, "bodies over the gate %.1f" % force_ref.gate(k_ref.max()), [(int(i), float(K[i])) for i in bad[:10]])
             else:
                 c.step_local()
                 c.commit()
