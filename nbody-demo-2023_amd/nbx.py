@@ -37,6 +37,9 @@ ENSEMBLE_SYMBOLS = (
     "nbx_ensemble_download", "nbx_ensemble_sync", "nbx_ensemble_profile", "nbx_ensemble_stats",
 )
 
+# the symbol of include/nbx_ensemble_diag.h (the diagnostics of every member of an ensemble in one launch), kept apart likewise
+ENSEMBLE_DIAG_SYMBOLS = ("nbx_ensemble_diagnostics",)
+
 
 class NbxError(RuntimeError):
     def __init__(self, code, where, text):
@@ -173,6 +176,8 @@ def load():
         L.nbx_ensemble_sync.argtypes = [vp]
         L.nbx_ensemble_profile.argtypes = [vp, i32]
         L.nbx_ensemble_stats.argtypes = [vp, ctypes.POINTER(EnsembleStats)]
+    if hasattr(L, "nbx_ensemble_diagnostics"):  # likewise for nbx_ensemble_diag.hip
+        L.nbx_ensemble_diagnostics.argtypes = [vp, i32, i32, ctypes.POINTER(Diag)]
     _lib = L
     return L
 
@@ -391,6 +396,19 @@ class Ensemble:
         s.struct_size = ctypes.sizeof(EnsembleStats)
         _check(self._L.nbx_ensemble_stats(self._h, ctypes.byref(s)), "nbx_ensemble_stats")
         return s.asdict()
+
+    def diagnostics(self, first=0, count=None):
+        """nbx_ensemble_diagnostics: one dict per member of [first, first + count) (default: all from `first`), each what
+        Context.diagnostics() returns for a context of n bodies holding that member's state -- the same bits; one launch for
+        all of them.  Synchronises."""
+        if not hasattr(self._L, "nbx_ensemble_diagnostics"):
+            raise NbxError(NBX_ERR_STATE, "nbx_ensemble_diagnostics", "%s was built without nbx_ensemble_diagnostics" % LIB_PATH)
+        count = self.members - first if count is None else count
+        d = (Diag * max(count, 1))()
+        for k in range(max(count, 0)):
+            d[k].struct_size = ctypes.sizeof(Diag)
+        _check(self._L.nbx_ensemble_diagnostics(self._h, first, count, d), "nbx_ensemble_diagnostics")
+        return [d[k].asdict() for k in range(max(count, 0))]
 
 
 class Group:
