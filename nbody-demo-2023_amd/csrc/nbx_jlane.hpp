@@ -1,8 +1,10 @@
 // nbx_jlane.hpp -- the one-launch-per-step kernel body (NBX_KERNEL_JLANE) as device functions, and what it reads its
-// arguments from.  Inline code only, so that two translation units can include it: nbx_kernels.hpp wraps the bodies into
+// arguments from.  Inline code only, so that several translation units can include it: nbx_kernels.hpp wraps the bodies into
 // force_jlane_kernel / force_jlane_kernel_f64 (one system per launch, nbx_api.hip), nbx_ensemble_kernels.hpp into
-// ensemble_step_kernel / ensemble_step_kernel_f64 (many systems per launch, nbx_ensemble.hip).  The workgroup index is an
-// argument: a context passes blockIdx.x, an ensemble too -- after it has pointed the arguments at member blockIdx.y.
+// ensemble_step_kernel / ensemble_step_kernel_f64 (many systems per launch, nbx_ensemble.hip), nbx_ragged_kernels.hpp into
+// ragged_step_kernel / ragged_step_kernel_f64 (systems of different size per launch, nbx_ragged.hip).  The workgroup index is an
+// argument: a context passes blockIdx.x, an ensemble too -- after it has pointed the arguments at member blockIdx.y -- and a
+// ragged ensemble the index its work list gives workgroup blockIdx.x within its member.
 #pragma once
 #include <hip/hip_runtime.h>
 

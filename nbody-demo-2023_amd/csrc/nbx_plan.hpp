@@ -1,10 +1,14 @@
 // nbx_plan.hpp -- which force kernel a context runs and with what launch shape: the policy of nbx_create, host-only.
 // Standard library and include/nbx.h only: no HIP call, no environment, no nbx_ctx, so that g++ compiles it without ROCm
 // (tests/test_launch_plan.py drives it with every nbx_opts).  kInstances is the one list of compiled force-kernel instances:
-// nbx_api.hip instantiates exactly those and launches the ones plan_launch names.
+// nbx_api.hip instantiates exactly those and launches the ones plan_launch names.  plan_ensemble and plan_ragged (below) are
+// the policies of nbx_ensemble_create and nbx_ragged_create, over kEnsembleInstances.
 #pragma once
 #include <algorithm>
 #include <cstddef>
+#include <cstdio>
+#include <numeric>
+#include <vector>
 
 #include "../../include/nbx.h"
 
@@ -223,18 +227,24 @@ inline int balanced_j_split(int bi, int cus, int max_s) {
 // the epilogue) is spread over twice the bodies and half as many waves stream a member's j records, which weighs most where the j
 // loop is short -- so their weight there is 0.97.  With fewer waves than SIMDs 16 lose as the table says (2048 x 4: 1.41 of 8's
 // time), and a lone system keeps the table it was measured with (16383 bodies: 8 per wave).
-inline int jlane_bodies_per_wave(int own, int members, int precision, int cus, int max_nb = 16) {
+// (`waves_of(nb)` = the launch's waves with nb bodies each: members x ceil(own / nb) for a context or an ensemble, the sum of
+// ceil(n_k / nb) over the members of a ragged ensemble -- one rule for all three)
+template <typename WavesOf>
+inline int jlane_bodies_per_wave_of(WavesOf&& waves_of, int members, int precision, int cus, int max_nb = 16) {
   max_nb = std::min(max_nb, precision == 32 ? 16 : 8);  // fp64 bodies take two SGPRs per coordinate
   int NB = 2;
   long long best = 0;
   for (int nb = 2; nb <= max_nb; nb *= 2) {
-    const long long waves = (long long)members * ceil_div(own, nb), simds = (long long)cus * 4;
+    const long long waves = waves_of(nb), simds = (long long)cus * 4;
     long long weight = precision != 32 ? 100 : (nb == 2 ? 129 : nb == 8 ? 100 : 106);
     if (precision == 32 && nb == 16 && members > 1 && waves >= simds) weight = 97;
     const long long cost = ((waves + simds - 1) / simds) * nb * weight;
     if (best == 0 || cost <= best) { best = cost; NB = nb; }
   }
   return NB;
+}
+inline int jlane_bodies_per_wave(int own, int members, int precision, int cus, int max_nb = 16) {
+  return jlane_bodies_per_wave_of([=](int nb) { return (long long)members * ceil_div(own, nb); }, members, precision, cus, max_nb);
 }
 // NBX_LOOP_AUTO, jlane kernel with a generated loop for its NB: the generated loop keeps four records per set in flight; with few
 // bodies per wave that is too little arithmetic to cover an L2 round trip when a SIMD holds a single wave, and the compiled loop
@@ -467,6 +477,123 @@ inline int plan_ensemble(int n, int precision, int members, int cus, const nbx_o
   p->NB = NB; p->loop = loop; p->D = jlane_depth(precision, NB);
   p->grid_x = ceil_div(ceil_div(n, NB), 4); p->grid_y = members;
   p->step = {INST_JLANE, precision, NB, 0, 0, 0, false, loop};
+  return NBX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Ragged ensembles (include/nbx_ragged.h): members of DIFFERENT size advanced by one launch per step.  The launch is a 1-D grid
+// whose workgroup blockIdx.x reads one RaggedWork descriptor -- which member it serves, which workgroup of that member it is and
+// where the member lives -- and runs the jlane kernel body on it, exactly as a context of n_k bodies with that NB and loop does.
+// ---------------------------------------------------------------------------------------------------------------------------
+// One workgroup's descriptor, as it lies on the device: 32 bytes, self-contained (one dependent scalar fetch per workgroup).
+struct RaggedWork {
+  unsigned pos_off;  // first record of the member in posm / posm_next
+  unsigned vel_off;  // first record of the member in velm
+  unsigned ke_off;   // first energy partial of the member in ke_part
+  unsigned wg;       // which workgroup of the member this is: [0, grid_k)
+  int n, n_alloc;    // the member's bodies, and its records (n rounded up to the tile; kSgprOverread spare records follow)
+  unsigned member;   // for the reader of a dump; the kernel does not need it
+  unsigned reserved;
+};
+static_assert(sizeof(RaggedWork) == 32, "a descriptor is at most one 8-dword scalar load, and the table index is a shift");
+struct RaggedMember {
+  unsigned pos_off, vel_off, ke_off;
+  int grid, n, n_alloc;  // grid: workgroups (= energy partials) of the member
+};
+
+struct RaggedPlan {
+  int members = 0, precision = 32;
+  int NB = 0, loop = LOOP_CXX, D = 0;
+  int W = 0;                              // workgroups of the launch: the sum of the members' grids
+  long long pos_records = 0;              // sum of n_alloc_k + kSgprOverread
+  long long vel_records = 0;              // sum of n_alloc_k
+  long long ke_parts = 0;                 // = W
+  long long bodies_total = 0;
+  int n_min = 0, n_max = 0;
+  double pairs_per_step = 0.0;            // sum of n_k^2
+  Instance step{};
+  std::vector<RaggedMember> member;       // by member index
+  std::vector<RaggedWork> work;           // by blockIdx.x: longest member first
+};
+
+// nbx_ragged_create's plan.  NBX_OK, or NBX_ERR_ARG with the text of nbx_last_error() in *msg (which may point into a
+// thread-local buffer where the text names a member).  Reads of `o`: as plan_ensemble.
+inline int plan_ragged(const int* n, int members, int precision, int cus, const nbx_opts& o, RaggedPlan* p, const char** msg) {
+  auto fail = [msg](const char* text) { *msg = text; return NBX_ERR_ARG; };
+  *p = RaggedPlan{};
+  if (cus <= 0) cus = 256;
+  if (precision != 32 && precision != 64) return fail("nbx_ragged_create: precision must be 32 or 64");
+  if (members < 1 || members > kEnsembleMaxMembers) return fail("nbx_ragged_create: members must be in [1, 65535]");
+  if (!n) return fail("nbx_ragged_create: n is NULL (the members' sizes)");
+  const int n_limit = precision == 32 ? kJlaneMaxOwn : kJlaneMaxOwnF64;
+  long long pos_records = 0;
+  for (int k = 0; k < members; ++k) {
+    if (n[k] < 1 || n[k] > n_limit) {
+      static thread_local char text[256];
+      std::snprintf(text, sizeof text,
+                    n[k] < 1 ? "nbx_ragged_create: n[%d] = %d: every member's n must be > 0"
+                             : "nbx_ragged_create: n[%d] = %d is beyond the one-launch kernel's range (fp32: 16383, fp64: 12288 bodies); a system of that size fills the card on its own: use nbx_create",
+                    k, n[k]);
+      return fail(text);
+    }
+    pos_records += round_up(n[k], kTile) + kSgprOverread;
+  }
+  // (cannot be reached with today's limits; it is what the 32-bit record offsets of RaggedWork rest on if they move)
+  if (pos_records > 0x7fffffffLL) return fail("nbx_ragged_create: the members' records and spare records together must fit 31 bits of record index");
+  if (o.kernel_variant != NBX_KERNEL_AUTO && o.kernel_variant != NBX_KERNEL_JLANE)
+    return fail("nbx_ragged_create: kernel_variant must be NBX_KERNEL_AUTO or NBX_KERNEL_JLANE (a member steps with the one-launch kernel body)");
+  if (o.summation_order != NBX_ORDER_AUTO && o.summation_order != NBX_ORDER_TREE)
+    return fail("nbx_ragged_create: summation_order must be NBX_ORDER_AUTO or NBX_ORDER_TREE (the one-launch kernel sums in tree order)");
+  if (o.j_split > 1) return fail("nbx_ragged_create: j_split must be 0 or 1 (a member's j range is not split over workgroups)");
+  if (o.i_begin != 0 || o.i_count != 0) return fail("nbx_ragged_create: i_begin and i_count must be 0 (a ragged ensemble is not sharded; run one per GPU)");
+  if (o.external_stream != 0) return fail("nbx_ragged_create: external_stream must be 0 (a ragged ensemble steps on a stream of its own)");
+  const int max_nb = precision == 32 ? 16 : 8;
+  int NB = o.bodies_per_lane;
+  if (NB != 0 && ((NB != 2 && NB != 4 && NB != 8 && NB != 16) || NB > max_nb))
+    return fail("nbx_ragged_create: bodies_per_lane must be 0 (auto), 2, 4, 8 or -- fp32 only -- 16 bodies per wave");
+  if (o.inner_loop != NBX_LOOP_AUTO && o.inner_loop != NBX_LOOP_CXX && o.inner_loop != NBX_LOOP_ASM)
+    return fail("nbx_ragged_create: inner_loop must be NBX_LOOP_AUTO, NBX_LOOP_CXX or NBX_LOOP_ASM");
+  // One NB and one loop for the whole launch (NB is a template argument): jlane_bodies_per_wave's rule with the waves of all
+  // members counted.  That members differ in j length does not enter -- nobody has measured whether it matters;
+  // scripts/ragged_sweep.py records the time of every NB next to the one taken here.
+  auto waves_of = [n, members](int nb) {
+    long long w = 0;
+    for (int k = 0; k < members; ++k) w += ceil_div(n[k], nb);
+    return w;
+  };
+  if (NB == 0) NB = jlane_bodies_per_wave_of(waves_of, members, precision, cus, o.inner_loop == NBX_LOOP_ASM && precision == 32 ? 8 : 16);
+  const bool asm_loop_compiled = ensemble_instance_index({INST_JLANE, precision, NB, 0, 0, 0, false, LOOP_ASM}) >= 0;
+  int loop = (o.inner_loop != NBX_LOOP_CXX && asm_loop_compiled) ? LOOP_ASM : LOOP_CXX;
+  if (o.inner_loop == NBX_LOOP_ASM && loop != LOOP_ASM)
+    return fail("nbx_ragged_create: no hand-scheduled loop for this shape (needs fp32 and 2, 4 or 8 bodies per wave)");
+  if (o.inner_loop == NBX_LOOP_AUTO && loop == LOOP_ASM && !jlane_auto_takes_generated_loop(NB, waves_of(NB), cus)) loop = LOOP_CXX;
+  p->members = members; p->precision = precision;
+  p->NB = NB; p->loop = loop; p->D = jlane_depth(precision, NB);
+  p->step = {INST_JLANE, precision, NB, 0, 0, 0, false, loop};
+  // members one behind the other, in member order
+  p->member.resize((size_t)members);
+  p->n_min = p->n_max = n[0];
+  long long pos = 0, vel = 0, ke = 0;
+  for (int k = 0; k < members; ++k) {
+    RaggedMember& m = p->member[(size_t)k];
+    m.n = n[k]; m.n_alloc = round_up(n[k], kTile); m.grid = ceil_div(ceil_div(n[k], NB), 4);
+    m.pos_off = (unsigned)pos; m.vel_off = (unsigned)vel; m.ke_off = (unsigned)ke;
+    pos += m.n_alloc + kSgprOverread; vel += m.n_alloc; ke += m.grid;
+    p->n_min = std::min(p->n_min, n[k]); p->n_max = std::max(p->n_max, n[k]);
+    p->bodies_total += n[k];
+    p->pairs_per_step += (double)n[k] * (double)n[k];
+  }
+  p->pos_records = pos; p->vel_records = vel; p->ke_parts = ke; p->W = (int)ke;
+  // Work order: the dispatcher hands out workgroups in index order, so the members with the longest j loop come first and
+  // never form the launch's tail (longest first; ties to the lower member index).  The member index a user sees is unaffected.
+  std::vector<int> order((size_t)members);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [p](int a, int b) { return p->member[(size_t)a].n_alloc > p->member[(size_t)b].n_alloc; });
+  p->work.reserve((size_t)p->W);
+  for (int k : order) {
+    const RaggedMember& m = p->member[(size_t)k];
+    for (int wg = 0; wg < m.grid; ++wg) p->work.push_back({m.pos_off, m.vel_off, m.ke_off, (unsigned)wg, m.n, m.n_alloc, (unsigned)k, 0u});
+  }
   return NBX_OK;
 }
 

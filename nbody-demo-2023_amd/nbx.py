@@ -40,6 +40,12 @@ ENSEMBLE_SYMBOLS = (
 # the symbol of include/nbx_ensemble_diag.h (the diagnostics of every member of an ensemble in one launch), kept apart likewise
 ENSEMBLE_DIAG_SYMBOLS = ("nbx_ensemble_diagnostics",)
 
+# the symbols of include/nbx_ragged.h (systems of different size in one launch), kept apart likewise
+RAGGED_SYMBOLS = (
+    "nbx_ragged_create", "nbx_ragged_destroy", "nbx_ragged_upload", "nbx_ragged_step", "nbx_ragged_step_trace",
+    "nbx_ragged_download", "nbx_ragged_sync", "nbx_ragged_profile", "nbx_ragged_stats",
+)
+
 
 class NbxError(RuntimeError):
     def __init__(self, code, where, text):
@@ -102,6 +108,20 @@ class EnsembleStats(ctypes.Structure):
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+class RaggedStats(ctypes.Structure):
+    """nbx_ragged_stats_t (include/nbx_ragged.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("members", ctypes.c_int32), ("precision", ctypes.c_int32), ("n_min", ctypes.c_int32),
+        ("n_max", ctypes.c_int32), ("bodies_total", ctypes.c_int32), ("bodies_per_lane", ctypes.c_int32), ("inner_loop", ctypes.c_int32),
+        ("grid_x", ctypes.c_int32), ("block", ctypes.c_int32), ("cu_count", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("pairs_per_step", ctypes.c_double), ("steps_done", ctypes.c_int64), ("launches_timed", ctypes.c_int64),
+        ("step_ms_total", ctypes.c_double),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k not in ("struct_size", "reserved")}
 
 
 _lib = None
@@ -178,6 +198,17 @@ def load():
         L.nbx_ensemble_stats.argtypes = [vp, ctypes.POINTER(EnsembleStats)]
     if hasattr(L, "nbx_ensemble_diagnostics"):  # likewise for nbx_ensemble_diag.hip
         L.nbx_ensemble_diagnostics.argtypes = [vp, i32, i32, ctypes.POINTER(Diag)]
+    if hasattr(L, "nbx_ragged_create"):  # likewise for nbx_ragged.hip
+        L.nbx_ragged_create.argtypes = [ctypes.POINTER(vp), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(Opts)]
+        L.nbx_ragged_destroy.argtypes = [vp]
+        L.nbx_ragged_destroy.restype = None
+        L.nbx_ragged_upload.argtypes = [vp, i32, i32] + [vp] * 7
+        L.nbx_ragged_step.argtypes = [vp, dbl, i32, vp]
+        L.nbx_ragged_step_trace.argtypes = [vp, dbl, i32, vp]
+        L.nbx_ragged_download.argtypes = [vp, i32, i32] + [vp] * 6
+        L.nbx_ragged_sync.argtypes = [vp]
+        L.nbx_ragged_profile.argtypes = [vp, i32]
+        L.nbx_ragged_stats.argtypes = [vp, ctypes.POINTER(RaggedStats)]
     _lib = L
     return L
 
@@ -409,6 +440,95 @@ class Ensemble:
             d[k].struct_size = ctypes.sizeof(Diag)
         _check(self._L.nbx_ensemble_diagnostics(self._h, first, count, d), "nbx_ensemble_diagnostics")
         return [d[k].asdict() for k in range(max(count, 0))]
+
+
+class Ragged:
+    """One nbx_ragged (include/nbx_ragged.h): independent systems of different size, member k of sizes[k] bodies, one launch per
+    time step for all of them.  Keyword options are the nbx_opts fields it honours (device, bodies_per_lane, inner_loop)."""
+
+    def __init__(self, sizes, precision=32, **opts):
+        self._L = load()
+        if not hasattr(self._L, "nbx_ragged_create"):
+            raise NbxError(NBX_ERR_STATE, "nbx_ragged_create", "%s was built without the ragged-ensemble entry points" % LIB_PATH)
+        self._h = ctypes.c_void_p()
+        self.sizes = [int(n) for n in sizes]
+        self.members, self.precision = len(self.sizes), int(precision)
+        o = Opts()
+        o.struct_size = ctypes.sizeof(Opts)
+        o.device = -1
+        for k, v in opts.items():
+            if not hasattr(o, k):
+                raise TypeError("unknown nbx_opts field %r" % k)
+            setattr(o, k, v)
+        n = (ctypes.c_int32 * max(self.members, 1))(*self.sizes)
+        _check(self._L.nbx_ragged_create(ctypes.byref(self._h), self.members, n, self.precision, ctypes.byref(o)), "nbx_ragged_create")
+        self.dtype = _dtype(self.precision)
+
+    def close(self):
+        if self._h:
+            self._L.nbx_ragged_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _range(self, first, count):
+        """The sizes of members [first, first + count), or [] where the range leaves [0, members) (the library names the error)."""
+        return self.sizes[first:first + count] if 0 <= first and 0 <= count and first + count <= self.members else []
+
+    def upload(self, states, first=0):
+        """Members first, first + 1, ...: a list of state dicts (what initial_conditions returns), member first + k of sizes[first + k] bodies."""
+        states = list(states)
+        sizes = self._range(first, len(states))
+        for k, n in enumerate(sizes):
+            for f in FIELDS:
+                if np.shape(states[k][f]) != (n,):
+                    raise NbxError(NBX_ERR_ARG, "array", "member %d: expected shape (%d,), got %r" % (first + k, n, np.shape(states[k][f])))
+        arrs = [np.ascontiguousarray(np.concatenate([np.asarray(s[f], dtype=self.dtype) for s in states]) if states
+                                     else np.zeros(0, dtype=self.dtype)) for f in FIELDS]
+        _check(self._L.nbx_ragged_upload(self._h, first, len(states), *[_ptr(a) for a in arrs]), "nbx_ragged_upload")
+
+    def step(self, nsteps, dt=DT, kenergy=True):
+        """nsteps steps of every member; the kinetic energy of each member after the last one (array of `members`) if asked for."""
+        ke = np.zeros(self.members, dtype=np.float64) if kenergy else None
+        _check(self._L.nbx_ragged_step(self._h, dt, nsteps, _ptr(ke)), "nbx_ragged_step")
+        return ke
+
+    def step_trace(self, nsteps, dt=DT):
+        """The kinetic energy of every member after every step: array (nsteps, members)."""
+        ke = np.zeros((max(nsteps, 1), self.members), dtype=np.float64)
+        _check(self._L.nbx_ragged_step_trace(self._h, dt, nsteps, _ptr(ke)), "nbx_ragged_step_trace")
+        return ke[:nsteps]
+
+    def download(self, first=0, count=None):
+        """Members [first, first + count) (default: all from `first`): a list of dicts of six arrays, one per member."""
+        count = self.members - first if count is None else count
+        sizes = self._range(first, count)
+        flat = {f: np.zeros(max(sum(sizes), 1), dtype=self.dtype) for f in FIELDS[:6]}
+        _check(self._L.nbx_ragged_download(self._h, first, count, *[_ptr(flat[f]) for f in FIELDS[:6]]), "nbx_ragged_download")
+        at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+        return [{f: flat[f][at[k]:at[k + 1]].copy() for f in FIELDS[:6]} for k in range(len(sizes))]
+
+    def sync(self):
+        _check(self._L.nbx_ragged_sync(self._h), "nbx_ragged_sync")
+
+    def profile(self, enable=True):
+        _check(self._L.nbx_ragged_profile(self._h, 1 if enable else 0), "nbx_ragged_profile")
+
+    def stats(self):
+        s = RaggedStats()
+        s.struct_size = ctypes.sizeof(RaggedStats)
+        _check(self._L.nbx_ragged_stats(self._h, ctypes.byref(s)), "nbx_ragged_stats")
+        return s.asdict()
 
 
 class Group:
