@@ -1,32 +1,17 @@
 // nbx_diag_body.hpp -- the device code of the physics diagnostics that more than one translation unit runs: the launch-shape
-// rule (diag_splits), the pair loop over one LDS tile (diag_tile), the work of one workgroup of diag_kernel (diag_body) and
+// rule (diag_splits, by way of nbx_diag_shape.hpp), the pair loop over one LDS tile (diag_tile), the work of one workgroup of diag_kernel (diag_body) and
 // the fixed-order sum of a block of partial rows (diag_reduce_rows).  nbx_diag_kernels.hpp wraps them in the kernels of a
-// context, nbx_ensemble_diag_kernels.hpp in the kernels of an ensemble; this header defines no kernel, so each of those
-// translation units compiles exactly the kernels it names.  What the code does is described in nbx_diag_kernels.hpp.
+// context, nbx_ensemble_diag_kernels.hpp in the kernels of an ensemble, nbx_ragged_diag_kernels.hpp in those of a ragged
+// ensemble; this header defines no kernel, so each of those translation units compiles exactly the kernels it names.  What the code does is described in nbx_diag_kernels.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "nbx_diag_shape.hpp"  // diag_splits and its constants, kDiagBodies: host-only, shared with nbx_plan.hpp
 #include "nbx_pair.hpp"
 
 namespace nbx {
 
 constexpr int kDiagFields = 9;
-template <typename T> constexpr int kDiagBodies = 2;  // bodies per lane (fp32: one packed pair)
-constexpr int kDiagTargetGroups = 1024;  // workgroups the j split aims at: 4 per CU of a 256-CU MI355X, 4 waves per SIMD
-constexpr int kDiagMinSplitTiles = 4;    // a split sums at least this many 256-record tiles
-
-// Number of j splits for `body_blocks` workgroup columns over `tiles` j tiles, and the tiles per split (every split
-// non-empty).  A function of the state's size only -- never of the context's force options -- so every context holding a
-// state sums it in the same order.
-inline void diag_splits(int body_blocks, int tiles, int* splits, int* tiles_per_split) {
-  int s = (kDiagTargetGroups + body_blocks - 1) / body_blocks;
-  const int max_s = tiles / kDiagMinSplitTiles;
-  if (s > max_s) s = max_s;
-  if (s < 1) s = 1;
-  const int per = (tiles + s - 1) / s;
-  *tiles_per_split = per;
-  *splits = (tiles + per - 1) / per;
-}
 
 // sum_{j in tile} G m_j / sqrt(|x_j - x_i|^2 + eps^2) for the lane's B bodies, in T.  MASK: the tile holds one of this
 // workgroup's bodies -- the term j == i is replaced by an exact 0 (j_glob is the global index of tile record 0).

@@ -1,8 +1,9 @@
 // nbx_plan.hpp -- which force kernel a context runs and with what launch shape: the policy of nbx_create, host-only.
-// Standard library and include/nbx.h only: no HIP call, no environment, no nbx_ctx, so that g++ compiles it without ROCm
+// Standard library, include/nbx.h and nbx_diag_shape.hpp (which includes nothing) only: no HIP call, no environment, no nbx_ctx, so that g++ compiles it without ROCm
 // (tests/test_launch_plan.py drives it with every nbx_opts).  kInstances is the one list of compiled force-kernel instances:
 // nbx_api.hip instantiates exactly those and launches the ones plan_launch names.  plan_ensemble and plan_ragged (below) are
-// the policies of nbx_ensemble_create and nbx_ragged_create, over kEnsembleInstances.
+// the policies of nbx_ensemble_create and nbx_ragged_create, over kEnsembleInstances; plan_ragged_diag is the work list of
+// nbx_ragged_diagnostics.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../include/nbx.h"
+#include "nbx_diag_shape.hpp"  // diag_splits: the shape rule of the diagnostics, read by plan_ragged_diag (host-only as well)
 
 namespace nbx_detail {
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -595,6 +597,75 @@ inline int plan_ragged(const int* n, int members, int precision, int cus, const 
     for (int wg = 0; wg < m.grid; ++wg) p->work.push_back({m.pos_off, m.vel_off, m.ke_off, (unsigned)wg, m.n, m.n_alloc, (unsigned)k, 0u});
   }
   return NBX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Diagnostics of the members of a ragged ensemble (include/nbx_ragged_diag.h): one pair-work launch over a 1-D grid whose
+// workgroup blockIdx.x reads one RaggedDiagWork descriptor and runs diag_body (nbx_diag_body.hpp) on it, one reduce launch over
+// the members asked for.  Member k's shape is exactly what enqueue_diag_t (nbx_diag.hip) gives a context of n_k bodies that owns
+// all of them: cols_k = ceil(n_k / (256 kDiagBodies)), (splits_k, per_k) = diag_splits(cols_k, ceil(n_k / 256)), rows_k =
+// cols_k splits_k partial rows -- diag_splits itself (nbx_diag_shape.hpp), not a restatement of it.
+// ---------------------------------------------------------------------------------------------------------------------------
+// One workgroup's descriptor, as it lies on the device: 32 bytes, self-contained for the reason RaggedWork is (one dependent
+// scalar fetch at a wave-uniform index).  The workgroup writes partial row row_off + split * cols + col, as diag_body counts rows.
+struct RaggedDiagWork {
+  unsigned pos_off;  // first record of the member in posm
+  unsigned vel_off;  // first record of the member in velm
+  unsigned row_off;  // first partial row of the member
+  int n;             // the member's bodies
+  int col, split;    // this workgroup: body column [0, cols), j split [0, splits)
+  int cols;          // the member's body columns
+  int tiles_per_split;
+};
+static_assert(sizeof(RaggedDiagWork) == 32, "a descriptor is at most one 8-dword scalar load, and the table index is a shift");
+struct RaggedDiagRows { unsigned row_off; int rows; };  // member k's partial rows [row_off, row_off + rows): what the reduce reads
+struct RaggedDiagShape { int cols, tiles, splits, tiles_per_split, rows; };
+
+struct RaggedDiagPlan {
+  long long total_rows = 0;                // partial rows of all members
+  long long total_groups = 0;              // workgroups of a launch over all members: one per row
+  std::vector<RaggedDiagShape> shape;      // by member index
+  std::vector<RaggedDiagRows> rows;        // by member index
+  std::vector<unsigned> work_begin;        // [members + 1]: prefix sum of the members' rows = of their workgroups
+  std::vector<RaggedDiagWork> work;        // member order; within a member by split, then by column
+};
+
+// The work list is in MEMBER order, where plan_ragged's is longest-first.  Under the ragged size limits (n <= 16383, so cols <= 32)
+// the kDiagTargetGroups bound of diag_splits never binds (it asks for 1024 / 32 = 32 splits at least, tiles / 4 <= 16 allow fewer),
+// and tiles_per_split <= 7 for every member: with fewer than 8 tiles there is one split of at most 7 tiles; from 8 tiles up
+// s = floor(tiles / 4) >= 2 and ceil(tiles / s) <= 7 (tiles = 4 s + r, r <= 3: 4 + ceil(r / s) <= 6; 7 occurs at tiles = 7
+// alone).  So every workgroup of the launch sums between 1 and 7 tiles for 512 bodies: there is no long tail to schedule
+// around.  With member order a range [first, first + count) of members is a contiguous slice of the list -- work_begin[first] ..
+// work_begin[first + count) -- so no call builds or uploads a list.  Nobody has measured whether another order is faster.
+inline void plan_ragged_diag(const RaggedPlan& rp, int precision, RaggedDiagPlan* d) {
+  *d = RaggedDiagPlan{};
+  const int B = precision == 32 ? kDiagBodies<float> : kDiagBodies<double>;
+  const size_t members = rp.member.size();
+  d->shape.resize(members);
+  d->rows.resize(members);
+  d->work_begin.assign(members + 1, 0u);
+  long long rows = 0;
+  for (size_t k = 0; k < members; ++k) {
+    const RaggedMember& m = rp.member[k];
+    RaggedDiagShape& s = d->shape[k];
+    s.cols = ceil_div(m.n, kBlock * B);
+    s.tiles = ceil_div(m.n, kTile);
+    diag_splits(s.cols, s.tiles, &s.splits, &s.tiles_per_split);
+    s.rows = s.cols * s.splits;
+    d->rows[k] = {(unsigned)rows, s.rows};
+    d->work_begin[k] = (unsigned)rows;
+    rows += s.rows;  // 65535 members x 512 rows at most: 25 bits
+  }
+  d->work_begin[members] = (unsigned)rows;
+  d->total_rows = d->total_groups = rows;
+  d->work.reserve((size_t)rows);
+  for (size_t k = 0; k < members; ++k) {
+    const RaggedMember& m = rp.member[k];
+    const RaggedDiagShape& s = d->shape[k];
+    for (int split = 0; split < s.splits; ++split)
+      for (int col = 0; col < s.cols; ++col)
+        d->work.push_back({m.pos_off, m.vel_off, d->rows[k].row_off, m.n, col, split, s.cols, s.tiles_per_split});
+  }
 }
 
 }  // namespace nbx

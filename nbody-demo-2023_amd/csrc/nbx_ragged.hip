@@ -15,39 +15,11 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/nbx_ragged.h"
-#include "nbx_internal.hpp"  // error plumbing; nbx_plan.hpp: nbx::RaggedPlan
+#include "nbx_ragged_internal.hpp"  // struct nbx_ragged; error plumbing; nbx_plan.hpp: nbx::RaggedPlan
 #include "nbx_ragged_kernels.hpp"
 
 using namespace nbx;
 using namespace nbx_detail;
-
-struct nbx_ragged {
-  int members = 0, precision = 32;
-  nbx::RaggedPlan plan;  // per-member offsets (plan.member) and the work list as uploaded (plan.work)
-  void (*launch_step)(nbx_ragged*, double dt) = nullptr;  // plan.step, resolved by nbx_ragged_create
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipDeviceProp_t prop{};
-  size_t rec = 16;  // bytes per {x,y,z,w} record
-  void* posm[2] = {nullptr, nullptr};
-  int cur = 0;
-  void* velm = nullptr;
-  double* ke_part = nullptr;           // [plan.W], a member's partials together
-  nbx::RaggedWork* work_dev = nullptr;   // [plan.W]
-  nbx::RaggedParts* parts_dev = nullptr; // [members]
-  bool have_parts = false;             // a step has written ke_part since the last upload
-  double* ke_dev = nullptr;            // [ke_cap] reduced sums (sum m v^2), slot s of member m at s * members + m
-  size_t ke_cap = 0;
-  std::vector<char> uploaded;          // per member
-  int uploaded_count = 0;
-  long long steps_done = 0;
-  bool profiling = false;
-  std::vector<hipEvent_t> ev;          // pairs start/stop
-  size_t ev_used = 0;
-  double step_ms_total = 0.0;
-  long long launches_timed = 0;
-};
 
 namespace {
 
@@ -346,6 +318,10 @@ void nbx_ragged_destroy(nbx_ragged* r) {
   if (r->work_dev) (void)hipFree(r->work_dev);
   if (r->parts_dev) (void)hipFree(r->parts_dev);
   if (r->ke_dev) (void)hipFree(r->ke_dev);
+  if (r->diag_work_dev) (void)hipFree(r->diag_work_dev);  // the buffers of nbx_ragged_diag.hip
+  if (r->diag_rows_dev) (void)hipFree(r->diag_rows_dev);
+  if (r->diag_part) (void)hipFree(r->diag_part);
+  if (r->diag_dev) (void)hipFree(r->diag_dev);
   if (r->stream) (void)hipStreamDestroy(r->stream);
   delete r;
 }

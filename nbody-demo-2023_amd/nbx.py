@@ -46,6 +46,9 @@ RAGGED_SYMBOLS = (
     "nbx_ragged_download", "nbx_ragged_sync", "nbx_ragged_profile", "nbx_ragged_stats",
 )
 
+# the symbol of include/nbx_ragged_diag.h (the diagnostics of every member of a ragged ensemble in one launch), kept apart likewise
+RAGGED_DIAG_SYMBOLS = ("nbx_ragged_diagnostics",)
+
 
 class NbxError(RuntimeError):
     def __init__(self, code, where, text):
@@ -209,6 +212,8 @@ def load():
         L.nbx_ragged_sync.argtypes = [vp]
         L.nbx_ragged_profile.argtypes = [vp, i32]
         L.nbx_ragged_stats.argtypes = [vp, ctypes.POINTER(RaggedStats)]
+    if hasattr(L, "nbx_ragged_diagnostics"):  # likewise for nbx_ragged_diag.hip
+        L.nbx_ragged_diagnostics.argtypes = [vp, i32, i32, ctypes.POINTER(Diag)]
     _lib = L
     return L
 
@@ -529,6 +534,19 @@ class Ragged:
         s.struct_size = ctypes.sizeof(RaggedStats)
         _check(self._L.nbx_ragged_stats(self._h, ctypes.byref(s)), "nbx_ragged_stats")
         return s.asdict()
+
+    def diagnostics(self, first=0, count=None):
+        """nbx_ragged_diagnostics: one dict per member of [first, first + count) (default: all from `first`), each what
+        Context.diagnostics() returns for a context of sizes[k] bodies holding that member's state -- the same bits; one launch
+        for all of them.  Synchronises."""
+        if not hasattr(self._L, "nbx_ragged_diagnostics"):
+            raise NbxError(NBX_ERR_STATE, "nbx_ragged_diagnostics", "%s was built without nbx_ragged_diagnostics" % LIB_PATH)
+        count = self.members - first if count is None else count
+        d = (Diag * max(count, 1))()
+        for k in range(max(count, 0)):
+            d[k].struct_size = ctypes.sizeof(Diag)
+        _check(self._L.nbx_ragged_diagnostics(self._h, first, count, d), "nbx_ragged_diagnostics")
+        return [d[k].asdict() for k in range(max(count, 0))]
 
 
 class Group:

@@ -8,13 +8,15 @@ name=$1; shift
 dir=$here/ab/$name
 rm -rf "$dir"; mkdir -p "$dir/pkg/csrc" "$dir/include"
 cp "$root"/nbody-demo-2023_amd/csrc/* "$dir/pkg/csrc/"
-cp "$root"/include/nbx.h "$root"/include/nbx_diag.h "$root"/include/nbx_ensemble.h "$root"/include/nbx_ensemble_diag.h "$dir/include/"
+cp "$root"/include/nbx.h "$root"/include/nbx_diag.h "$root"/include/nbx_ensemble.h "$root"/include/nbx_ensemble_diag.h \
+   "$root"/include/nbx_ragged.h "$root"/include/nbx_ragged_diag.h "$dir/include/"
 env "$@" python3 "$here/gen_sgpr_loop.py" "$dir/pkg/csrc/nbx_sgpr_loop.inc"
 flags="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -fhip-fp32-correctly-rounded-divide-sqrt"
 # csrc includes "../../include/nbx_diag.h" (which includes nbx.h) relative to pkg/csrc -> $dir/include
 (cd "$dir/pkg/csrc" && hipcc $flags -c nbx_api.hip -o ../nbx_api.o && hipcc $flags -c nbx_group.hip -o ../nbx_group.o &&
  hipcc $flags -c nbx_diag.hip -o ../nbx_diag.o && hipcc $flags -c nbx_ensemble.hip -o ../nbx_ensemble.o &&
  hipcc $flags -c nbx_ensemble_diag.hip -o ../nbx_ensemble_diag.o &&
+ hipcc $flags -c nbx_ragged.hip -o ../nbx_ragged.o && hipcc $flags -c nbx_ragged_diag.hip -o ../nbx_ragged_diag.o &&
  hipcc -O2 -std=c++17 -fPIC -ffp-contract=off -c nbx_ic.cpp -o ../nbx_ic.o)
 hipcc --offload-arch=gfx950 -shared -fPIC -o "$dir/libnbx.so" "$dir"/pkg/*.o -ldl
 echo "built $dir/libnbx.so"
