@@ -1,0 +1,530 @@
+// nbx_batch.hpp -- the host side that ensembles (nbx_ensemble.hip, nbx_ensemble_diag.hip) and ragged ensembles (nbx_ragged.hip,
+// nbx_ragged_diag.hip) share: the fields both objects have, device choice, the energy trace, profiling, the member checks, the
+// step loop, the launcher table, upload and download over a member-layout lookup, create / destroy, and the diagnostics entry
+// point.  Host-only: it defines no kernel and includes no kernel header, so every translation unit keeps compiling exactly the
+// kernels it includes itself.
+//
+// A kind is a struct derived from Batch (nbx_ensemble, nbx_ragged) that adds
+//   static constexpr BatchNames names;           the words its error texts are made of
+//   MemberSpan layout(int k) const;              where member k lies on the device
+//   void (*launch_step)(Kind*, double dt);       one time step of all members, resolved at create from kLaunchers
+// and whose internal header declares the overload  int nbx_detail::enqueue_ke_reduce(Kind*, int slot)  (the step loop below
+// finds it by argument-dependent lookup); the kind's main translation unit defines it: it launches that unit's own reduce kernel.
+// The context (nbx_api.hip, nbx_group.hip) has helpers of the same names over nbx_ctx; its step path is tied to graph replay
+// and the exchange protocol and is not served from here.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <array>
+#include <cstring>
+#include <new>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "nbx_internal.hpp"  // error plumbing, diag_fill; nbx_plan.hpp: kEnsembleInstances, kSgprOverread
+#include "nbx_pair.hpp"      // the record types and the constants a record carries (inline code only, no kernel)
+
+// Nothing of this layer is visible outside the library: libnbx.so exports what the public headers declare, as before.
+#pragma GCC visibility push(hidden)
+namespace nbx_detail {
+
+struct BatchNames {
+  const char* prefix;  // "nbx_ensemble": the upload hint and the energy-trace text
+  const char* noun;    // "ensemble", as in "ensemble is NULL"
+};
+
+// Member k on the device: its first record in posm / velm, its bodies, and its records (n rounded up to the tile; kSgprOverread
+// spare records follow them in posm).
+struct MemberSpan {
+  size_t pos_off, vel_off;
+  int n, n_alloc;
+};
+
+struct Batch {
+  int members = 0, precision = 32;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipDeviceProp_t prop{};
+  size_t rec = 16;  // bytes per {x,y,z,w} record
+  void* posm[2] = {nullptr, nullptr};
+  int cur = 0;
+  void* velm = nullptr;
+  double* ke_part = nullptr;   // the step kernel's energy partials, a member's together
+  bool have_parts = false;     // a step has written ke_part since the last upload
+  double* ke_dev = nullptr;    // [ke_cap] reduced sums (sum m v^2), slot s of member m at s * members + m
+  size_t ke_cap = 0;
+  std::vector<char> uploaded;  // per member
+  int uploaded_count = 0;
+  long long steps_done = 0;
+  bool profiling = false;
+  std::vector<hipEvent_t> ev;  // pairs start/stop
+  size_t ev_used = 0;
+  double step_ms_total = 0.0;
+  long long launches_timed = 0;
+  // diagnostics (nbx_*_diag.hip): per-workgroup partials [rows][9] and the reduced fields [members][9], allocated on first use
+  double* diag_part = nullptr;
+  double* diag_dev = nullptr;
+};
+
+constexpr int kMaxProfiledLaunches = 8192;
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// device selection, energy trace, profiling
+// ---------------------------------------------------------------------------------------------------------------------------
+inline int use_device(Batch* b) {
+  HIP_TRY(hipSetDevice(b->device));
+  return NBX_OK;
+}
+
+inline int ensure_ke_cap(Batch* b, const char* prefix, size_t need) {
+  if (need <= b->ke_cap) return NBX_OK;
+  if (b->ke_dev) HIP_TRY(hipFree(b->ke_dev));
+  b->ke_dev = nullptr;
+  b->ke_cap = 0;
+  hipError_t err = hipMalloc(&b->ke_dev, sizeof(double) * need);
+  if (err != hipSuccess)
+    return fail(err == hipErrorOutOfMemory ? NBX_ERR_ALLOC : NBX_ERR_DEVICE,
+                std::string(prefix) + ": hipMalloc of the energy trace: " + hipGetErrorString(err));
+  b->ke_cap = need;
+  return NBX_OK;
+}
+
+inline int drain_profile(Batch* b) {
+  for (size_t k = 0; k + 1 < b->ev_used; k += 2) {
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, b->ev[k], b->ev[k + 1]));
+    b->step_ms_total += ms;
+    b->launches_timed += 1;
+  }
+  b->ev_used = 0;
+  return NBX_OK;
+}
+
+template <typename O>
+int batch_sync(O* o, const char* where) {
+  return guarded(where, [&]() -> int {
+  if (!o) return fail(NBX_ERR_ARG, std::string(where) + ": " + O::names.noun + " is NULL");
+  int rc = use_device(o);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(o->stream));
+  return NBX_OK;
+  });
+}
+
+template <typename O>
+int batch_profile(O* o, const char* where, int32_t enable) {
+  return guarded(where, [&]() -> int {
+  if (!o) return fail(NBX_ERR_ARG, std::string(where) + ": " + O::names.noun + " is NULL");
+  int rc = use_device(o);
+  if (rc) return rc;
+  if (enable && o->ev.empty()) {
+    o->ev.assign(2 * kMaxProfiledLaunches, nullptr);
+    for (auto& ev : o->ev) HIP_TRY(hipEventCreate(&ev));
+  }
+  if (!enable && o->profiling) {
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    rc = drain_profile(o);
+    if (rc) return rc;
+  }
+  if (enable && !o->profiling) {
+    o->step_ms_total = 0.0;
+    o->launches_timed = 0;
+    o->ev_used = 0;
+  }
+  o->profiling = enable != 0;
+  return NBX_OK;
+  });
+}
+
+// *_stats up to the fields of the kind: the checks, the pending events drained, *s cleared and the fields every kind reports
+// filled in; `fill(s)` adds the rest.  S is the kind's public stats struct, named where + "_t".
+template <typename O, typename S, typename Fill>
+int batch_stats(O* o, S* s, const char* where, Fill fill) {
+  return guarded(where, [&]() -> int {
+  if (!o || !s) return fail(NBX_ERR_ARG, std::string(where) + ": NULL argument");
+  if (s->struct_size != 0 && s->struct_size != (int32_t)sizeof(S))
+    return fail(NBX_ERR_ARG, std::string(where) + ": " + where + "_t.struct_size does not match this library");
+  int rc = use_device(o);
+  if (rc) return rc;
+  if (o->ev_used) {
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    rc = drain_profile(o);
+    if (rc) return rc;
+  }
+  std::memset(s, 0, sizeof(*s));
+  s->struct_size = (int32_t)sizeof(S);
+  s->members = o->members; s->precision = o->precision; s->block = nbx::kBlock; s->cu_count = o->prop.multiProcessorCount;
+  s->steps_done = o->steps_done; s->launches_timed = o->launches_timed; s->step_ms_total = o->step_ms_total;
+  fill(s);
+  return NBX_OK;
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// member checks
+// ---------------------------------------------------------------------------------------------------------------------------
+inline int check_range(const Batch* b, const char* where, int first, int count) {
+  if (first < 0 || count < 0 || (long long)first + count > b->members)
+    return fail(NBX_ERR_ARG, std::string(where) + ": members [first, first + count) are outside [0, members)");
+  return NBX_OK;
+}
+
+inline int check_uploaded(const Batch* b, const char* where, int first, int count) {
+  for (int k = first; k < first + count; ++k)
+    if (!b->uploaded[k]) return fail(NBX_ERR_STATE, std::string(where) + ": member " + std::to_string(k) + " has not been uploaded");
+  return NBX_OK;
+}
+
+inline void mark_uploaded(Batch* b, int first, int count) {
+  for (int k = first; k < first + count; ++k)
+    if (!b->uploaded[k]) { b->uploaded[k] = 1; b->uploaded_count += 1; }
+  b->have_parts = false;  // the partials on the device belong to the previous trajectories
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// device buffers allocated after create (the diagnostics'); `where` is the entry point the text names
+// ---------------------------------------------------------------------------------------------------------------------------
+template <typename P>
+int device_alloc(P** p, size_t count, const char* where, const char* what) {
+  const hipError_t err = hipMalloc(p, sizeof(P) * count);
+  if (err == hipSuccess) return NBX_OK;
+  *p = nullptr;
+  return fail(err == hipErrorOutOfMemory ? NBX_ERR_ALLOC : NBX_ERR_DEVICE,
+              std::string(where) + ": hipMalloc of " + what + ": " + hipGetErrorString(err));
+}
+
+// a host table (which lives as long as the object) -> a device copy, on the stream the launches follow on; *p is set only once
+// the copy has been enqueued
+template <typename P>
+int device_table(Batch* b, P** p, const std::vector<P>& src, const char* where, const char* what) {
+  P* dev = nullptr;
+  const int rc = device_alloc(&dev, src.size(), where, what);
+  if (rc) return rc;
+  const hipError_t err = hipMemcpyAsync(dev, src.data(), sizeof(P) * src.size(), hipMemcpyHostToDevice, b->stream);
+  if (err != hipSuccess) {
+    (void)hipFree(dev);
+    return fail(NBX_ERR_DEVICE, std::string(where) + ": copy of " + what + ": " + hipGetErrorString(err));
+  }
+  *p = dev;
+  return NBX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// the step loop: one launch per step through o->launch_step, no allocation and no indirect call besides it
+// ---------------------------------------------------------------------------------------------------------------------------
+template <typename O>
+int enqueue_step(O* o, double dt) {
+  const bool prof = o->profiling && o->ev_used + 2 <= o->ev.size();
+  if (prof) HIP_TRY(hipEventRecord(o->ev[o->ev_used], o->stream));
+  o->launch_step(o, dt);
+  if (prof) {
+    HIP_TRY(hipEventRecord(o->ev[o->ev_used + 1], o->stream));
+    o->ev_used += 2;
+  }
+  HIP_TRY(hipGetLastError());
+  o->have_parts = true;
+  return NBX_OK;
+}
+
+// *_step (ke_trace == nullptr) and, behind step_trace below, *_step_trace (ke_last == nullptr)
+template <typename O>
+int step_common(O* o, const char* where, double dt, int32_t nsteps, double* ke_last, double* ke_trace) {
+  return guarded(where, [&]() -> int {
+  if (!o) return fail(NBX_ERR_ARG, std::string(where) + ": " + O::names.noun + " is NULL");
+  if (nsteps < 0) return fail(NBX_ERR_ARG, std::string(where) + ": nsteps < 0");
+  if (o->uploaded_count != o->members)
+    return fail(NBX_ERR_STATE, std::string(where) + ": " + std::to_string(o->members - o->uploaded_count) + " of " + std::to_string(o->members) +
+                                   " members have not been uploaded (" + O::names.prefix + "_upload)");
+  int rc = use_device(o);
+  if (rc) return rc;
+  const size_t S = (size_t)o->members;
+  if (ke_trace || ke_last) {
+    rc = ensure_ke_cap(o, O::names.prefix, S * (size_t)(ke_trace ? std::max(nsteps, 1) : 1));
+    if (rc) return rc;
+  }
+  for (int s = 0; s < nsteps; ++s) {
+    rc = enqueue_step(o, dt);
+    if (rc) return rc;
+    o->cur ^= 1;
+    o->steps_done += 1;
+    if (ke_trace) rc = enqueue_ke_reduce(o, s);
+    else if (ke_last && s == nsteps - 1) rc = enqueue_ke_reduce(o, 0);
+    if (rc) return rc;
+  }
+  if (ke_trace && nsteps > 0) {
+    HIP_TRY(hipMemcpyAsync(ke_trace, o->ke_dev, sizeof(double) * S * (size_t)nsteps, hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    for (size_t k = 0; k < S * (size_t)nsteps; ++k) ke_trace[k] *= 0.5;  // ver7/GSimulation.cpp:200
+  } else if (ke_last) {
+    if (nsteps > 0 || o->have_parts) {
+      if (nsteps == 0) {
+        rc = enqueue_ke_reduce(o, 0);
+        if (rc) return rc;
+      }
+      HIP_TRY(hipMemcpyAsync(ke_last, o->ke_dev, sizeof(double) * S, hipMemcpyDeviceToHost, o->stream));
+      HIP_TRY(hipStreamSynchronize(o->stream));
+      for (size_t m = 0; m < S; ++m) ke_last[m] *= 0.5;
+    } else {
+      for (size_t m = 0; m < S; ++m) ke_last[m] = 0.0;
+    }
+  }
+  return NBX_OK;
+  });
+}
+
+// a NULL ke_trace is reported before the handle is looked at
+template <typename O>
+int step_trace(O* o, const char* where, double dt, int32_t nsteps, double* ke_trace) {
+  if (!ke_trace) return guarded(where, [&]() -> int { return fail(NBX_ERR_ARG, std::string(where) + ": ke_trace is NULL"); });
+  return step_common(o, where, dt, nsteps, nullptr, ke_trace);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// the launcher table: one launcher per entry of kEnsembleInstances -- the shapes a jlane context can run, and the only step-kernel
+// instances a kind's translation unit compiles.  Launch::run<I>(o, dt) launches the kind's kernel for entry I.
+// ---------------------------------------------------------------------------------------------------------------------------
+template <typename O, typename Launch, int I>
+void launch_instance(O* o, double dt) {
+  static_assert(nbx::kEnsembleInstances[I].kind == nbx::INST_JLANE, "a member steps with the one-launch kernel body");
+  Launch::template run<I>(o, dt);
+}
+template <typename O, typename Launch, int... I>
+constexpr std::array<void (*)(O*, double), sizeof...(I)> make_launchers(std::integer_sequence<int, I...>) {
+  return {{&launch_instance<O, Launch, I>...}};
+}
+template <typename O, typename Launch>
+constexpr auto kLaunchers = make_launchers<O, Launch>(std::make_integer_sequence<int, nbx::kEnsembleInstanceCount>{});
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// upload and download
+// ---------------------------------------------------------------------------------------------------------------------------
+// Members [first, first + count) lie one behind the other on the device: records [pos_begin, pos_begin + pos_count) of posm,
+// [vel_begin, vel_begin + vel_count) of velm.  For an ensemble (member k at k * pos_stride and k * own_pad, pos_stride =
+// n_alloc + kSgprOverread, own_pad = n_alloc) the counts are (count - 1) * stride + the last member's = count * pos_stride and
+// count * own_pad.
+struct Span { size_t pos_begin, pos_count, vel_begin, vel_count; };
+template <typename O>
+Span span_of(const O* o, int first, int count) {
+  const MemberSpan a = o->layout(first), b = o->layout(first + count - 1);
+  return {a.pos_off, b.pos_off + b.n_alloc + nbx::kSgprOverread - a.pos_off, a.vel_off, b.vel_off + b.n_alloc - a.vel_off};
+}
+
+// The host arrays hold the members one after the other, member `first` at element 0.
+template <typename T, typename O>
+int upload_t(O* o, int first, int count, const T* px, const T* py, const T* pz, const T* vx, const T* vy, const T* vz, const T* m) {
+  using T4 = typename nbx::V4<T>::type;
+  // the members' records as they lie on the device, padding and spare records included (zero): one copy per buffer
+  const Span sp = span_of(o, first, count);
+  T4 zero; zero.x = zero.y = zero.z = zero.w = (T)0;
+  std::vector<T4> hp(sp.pos_count, zero), hv(sp.vel_count, zero);
+  const T G = nbx::grav_const<T>();
+  size_t h = 0;  // the member's first element in the host arrays
+  for (int k = first; k < first + count; ++k) {
+    const MemberSpan mem = o->layout(k);
+    T4* p = hp.data() + (mem.pos_off - sp.pos_begin);
+    T4* v = hv.data() + (mem.vel_off - sp.vel_begin);
+    for (int i = 0; i < mem.n; ++i) {
+      T4 q; q.x = px[h + i]; q.y = py[h + i]; q.z = pz[h + i]; q.w = (G * m[h + i]) * nbx::gm_prescale<T>();
+      p[i] = q;
+      T4 u; u.x = vx[h + i]; u.y = vy[h + i]; u.z = vz[h + i]; u.w = m[h + i];
+      v[i] = u;
+    }
+    h += (size_t)mem.n;
+  }
+  const size_t pos_off = sizeof(T4) * sp.pos_begin, vel_off = sizeof(T4) * sp.vel_begin;
+  HIP_TRY(hipMemcpyAsync((char*)o->posm[0] + pos_off, hp.data(), sizeof(T4) * hp.size(), hipMemcpyHostToDevice, o->stream));
+  HIP_TRY(hipMemcpyAsync((char*)o->posm[1] + pos_off, hp.data(), sizeof(T4) * hp.size(), hipMemcpyHostToDevice, o->stream));
+  HIP_TRY(hipMemcpyAsync((char*)o->velm + vel_off, hv.data(), sizeof(T4) * hv.size(), hipMemcpyHostToDevice, o->stream));
+  HIP_TRY(hipStreamSynchronize(o->stream));
+  return NBX_OK;
+}
+
+// one buffer's records of members [first, first + count) -> up to three host arrays (a NULL one is skipped)
+template <typename T, typename O>
+int download_records(O* o, int first, int count, const void* dev, bool is_pos, T* x, T* y, T* z) {
+  using T4 = typename nbx::V4<T>::type;
+  if (!x && !y && !z) return NBX_OK;
+  const Span sp = span_of(o, first, count);
+  const size_t begin = is_pos ? sp.pos_begin : sp.vel_begin;
+  std::vector<T4> hr(is_pos ? sp.pos_count : sp.vel_count);
+  HIP_TRY(hipMemcpyAsync(hr.data(), (const char*)dev + sizeof(T4) * begin, sizeof(T4) * hr.size(), hipMemcpyDeviceToHost, o->stream));
+  HIP_TRY(hipStreamSynchronize(o->stream));
+  size_t h = 0;
+  for (int k = first; k < first + count; ++k) {
+    const MemberSpan mem = o->layout(k);
+    const T4* r = hr.data() + ((is_pos ? mem.pos_off : mem.vel_off) - begin);
+    for (int i = 0; i < mem.n; ++i) {
+      if (x) x[h + i] = r[i].x;
+      if (y) y[h + i] = r[i].y;
+      if (z) z[h + i] = r[i].z;
+    }
+    h += (size_t)mem.n;
+  }
+  return NBX_OK;
+}
+
+template <typename T, typename O>
+int download_t(O* o, int first, int count, T* px, T* py, T* pz, T* vx, T* vy, T* vz) {
+  const int rc = download_records(o, first, count, o->posm[o->cur], true, px, py, pz);
+  return rc ? rc : download_records(o, first, count, o->velm, false, vx, vy, vz);
+}
+
+template <typename O>
+int batch_upload(O* o, const char* where, int32_t first, int32_t count, const void* px, const void* py, const void* pz,
+                 const void* vx, const void* vy, const void* vz, const void* m) {
+  return guarded(where, [&]() -> int {
+  if (!o) return fail(NBX_ERR_ARG, std::string(where) + ": " + O::names.noun + " is NULL");
+  int rc = check_range(o, where, first, count);
+  if (rc) return rc;
+  if (!px || !py || !pz || !vx || !vy || !vz || !m) return fail(NBX_ERR_ARG, std::string(where) + ": NULL array");
+  if (count == 0) return NBX_OK;
+  rc = use_device(o);
+  if (rc) return rc;
+  rc = o->precision == 32
+           ? upload_t<float>(o, first, count, (const float*)px, (const float*)py, (const float*)pz, (const float*)vx, (const float*)vy,
+                             (const float*)vz, (const float*)m)
+           : upload_t<double>(o, first, count, (const double*)px, (const double*)py, (const double*)pz, (const double*)vx,
+                              (const double*)vy, (const double*)vz, (const double*)m);
+  if (rc) return rc;
+  mark_uploaded(o, first, count);
+  return NBX_OK;
+  });
+}
+
+template <typename O>
+int batch_download(O* o, const char* where, int32_t first, int32_t count, void* px, void* py, void* pz, void* vx, void* vy, void* vz) {
+  return guarded(where, [&]() -> int {
+  if (!o) return fail(NBX_ERR_ARG, std::string(where) + ": " + O::names.noun + " is NULL");
+  int rc = check_range(o, where, first, count);
+  if (rc) return rc;
+  rc = check_uploaded(o, where, first, count);
+  if (rc) return rc;
+  if (count == 0) return NBX_OK;
+  rc = use_device(o);
+  if (rc) return rc;
+  return o->precision == 32
+             ? download_t<float>(o, first, count, (float*)px, (float*)py, (float*)pz, (float*)vx, (float*)vy, (float*)vz)
+             : download_t<double>(o, first, count, (double*)px, (double*)py, (double*)pz, (double*)vx, (double*)vy, (double*)vz);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// create and destroy.  A *_create is: create_opts, the kind's planning (every argument check before the first HIP call),
+// batch_open, planning again with the CU count, the kind's own buffers under CREATE_TRY, owner.release().
+// ---------------------------------------------------------------------------------------------------------------------------
+#define CREATE_TRY(where, expr)                                                              \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess) {                                                                  \
+      std::string m_ = std::string(where) + ": " #expr ": " + hipGetErrorString(e_);         \
+      return fail(e_ == hipErrorOutOfMemory ? NBX_ERR_ALLOC : NBX_ERR_DEVICE, m_);           \
+    }                                                                                        \
+  } while (0)
+
+// frees the object on every failure path of *_create
+template <typename O>
+struct BatchOwner {
+  void (*destroy)(O*);
+  O* o = nullptr;
+  ~BatchOwner() { if (o) destroy(o); }
+  O* release() { O* p = o; o = nullptr; return p; }
+};
+
+// *out cleared, the caller's options or the defaults -> *o
+template <typename O>
+int create_opts(const char* where, O** out, const nbx_opts* opts, nbx_opts* o) {
+  if (!out) return fail(NBX_ERR_ARG, std::string(where) + ": out is NULL");
+  *out = nullptr;
+  std::memset(o, 0, sizeof(*o));
+  o->device = -1;
+  if (opts) {
+    if (opts->struct_size != 0 && opts->struct_size != (int32_t)sizeof(nbx_opts))
+      return fail(NBX_ERR_ARG, std::string(where) + ": nbx_opts.struct_size does not match this library");
+    *o = *opts;
+  }
+  return NBX_OK;
+}
+
+// the device, the object (owned by *owner from here on) and its stream; prop.multiProcessorCount is known afterwards
+template <typename O>
+int batch_open(const char* where, const nbx_opts& o, int members, int precision, BatchOwner<O>* owner) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(NBX_ERR_DEVICE, std::string(where) + ": no HIP device available (libnbx has no CPU path)");
+  int dev = o.device;
+  if (dev < 0) {
+    if (hipGetDevice(&dev) != hipSuccess) return fail(NBX_ERR_DEVICE, std::string(where) + ": hipGetDevice failed");
+  }
+  if (dev >= ndev) return fail(NBX_ERR_ARG, std::string(where) + ": device ordinal out of range");
+
+  O* b = new (std::nothrow) O();
+  if (!b) return fail(NBX_ERR_ALLOC, std::string(where) + ": out of host memory");
+  owner->o = b;
+  b->device = dev;
+  b->members = members;
+  b->precision = precision;
+  b->rec = precision == 32 ? sizeof(float4) : sizeof(double4);
+  b->uploaded.assign((size_t)members, 0);
+  CREATE_TRY(where, hipSetDevice(dev));
+  CREATE_TRY(where, hipGetDeviceProperties(&b->prop, dev));
+  CREATE_TRY(where, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+  return NBX_OK;
+}
+
+// plan.step -> o->launch_step
+template <typename O, typename Launch>
+int resolve_launcher(O* o, const char* where) {
+  const int k = nbx::ensemble_instance_index(o->plan.step);
+  if (k < 0) return fail(NBX_ERR_ARG, std::string(where) + ": no kernel instance for this bodies_per_lane / precision");
+  o->launch_step = kLaunchers<O, Launch>[k];
+  return NBX_OK;
+}
+
+// A *_destroy is: batch_quiesce, free what the kind owns, batch_release, delete.  The stream is synchronised first and
+// destroyed last.
+inline void batch_quiesce(Batch* b) {
+  (void)hipSetDevice(b->device);
+  if (b->stream) (void)hipStreamSynchronize(b->stream);
+}
+
+inline void batch_release(Batch* b) {
+  for (hipEvent_t ev : b->ev)
+    if (ev) (void)hipEventDestroy(ev);
+  for (void* p : {b->posm[0], b->posm[1], b->velm, (void*)b->ke_part, (void*)b->ke_dev, (void*)b->diag_part, (void*)b->diag_dev})
+    if (p) (void)hipFree(p);
+  if (b->stream) (void)hipStreamDestroy(b->stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// *_diagnostics: `enqueue(T{}, o, first, count)`, T the precision's type, enqueues the kind's kernels on o->stream; they leave
+// Fields raw sums per member in o->diag_dev[k * Fields ...], k = 0 .. count - 1
+// ---------------------------------------------------------------------------------------------------------------------------
+template <int Fields, typename O, typename Enqueue>
+int batch_diagnostics(O* o, const char* where, int32_t first, int32_t count, nbx_diag_t* out, Enqueue enqueue) {
+  static_assert(Fields == kDiagFieldCount, "diag_fill reads kDiagFieldCount raw sums per member");
+  return guarded(where, [&]() -> int {
+  if (!o || !out) return fail(NBX_ERR_ARG, std::string(where) + ": NULL argument");
+  int rc = check_range(o, where, first, count);
+  if (rc) return rc;
+  for (int k = 0; k < count; ++k)
+    if (out[k].struct_size != 0 && out[k].struct_size != (int32_t)sizeof(nbx_diag_t))
+      return fail(NBX_ERR_ARG, std::string(where) + ": out[" + std::to_string(k) + "].struct_size does not match this library");
+  rc = check_uploaded(o, where, first, count);
+  if (rc) return rc;
+  if (count == 0) return NBX_OK;
+  rc = use_device(o);
+  if (rc) return rc;
+  rc = o->precision == 32 ? enqueue(float{}, o, first, count) : enqueue(double{}, o, first, count);
+  if (rc) return rc;
+  std::vector<double> raw((size_t)count * Fields);
+  HIP_TRY(hipMemcpyAsync(raw.data(), o->diag_dev, sizeof(double) * raw.size(), hipMemcpyDeviceToHost, o->stream));
+  HIP_TRY(hipStreamSynchronize(o->stream));
+  for (int k = 0; k < count; ++k) diag_fill(raw.data() + (size_t)k * Fields, o->layout(first + k).n, o->steps_done, out + k);
+  return NBX_OK;
+  });
+}
+
+}  // namespace nbx_detail
+#pragma GCC visibility pop

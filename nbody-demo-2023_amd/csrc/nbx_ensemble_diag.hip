@@ -8,27 +8,16 @@
 // are the bits.  The call reads posm[cur] and velm and writes buffers of its own: the trajectory does not see it.
 #include <hip/hip_runtime.h>
 
-#include <string>
-#include <vector>
-
 #include "../../include/nbx_ensemble_diag.h"
 #include "nbx_ensemble_diag_kernels.hpp"
-#include "nbx_ensemble_internal.hpp"
+#include "nbx_ensemble_internal.hpp"  // struct nbx_ensemble; nbx_batch.hpp: batch_diagnostics, device_alloc
 
 using namespace nbx;
 using namespace nbx_detail;
 
-static_assert(kDiagFields == kDiagFieldCount, "diag_fill reads kDiagFieldCount raw sums per member");
-
 namespace {
 
-int device_alloc(double** p, size_t doubles, const char* what) {
-  const hipError_t err = hipMalloc(p, sizeof(double) * doubles);
-  if (err == hipSuccess) return NBX_OK;
-  *p = nullptr;
-  return fail(err == hipErrorOutOfMemory ? NBX_ERR_ALLOC : NBX_ERR_DEVICE,
-              std::string("nbx_ensemble_diagnostics: hipMalloc of ") + what + ": " + hipGetErrorString(err));
-}
+constexpr const char* kWhere = "nbx_ensemble_diagnostics";
 
 // members [first, first + count) -> e->diag_dev[k * kDiagFields ...], k = 0 .. count - 1, on the ensemble's stream
 template <typename T>
@@ -40,11 +29,11 @@ int enqueue_ensemble_diag_t(nbx_ensemble* e, int first, int count) {
   diag_splits(columns, ceil_div(e->n, kTile), &splits, &per);
   const int parts = columns * splits;  // n is fixed for the ensemble's life: so are the sizes of diag_part and diag_dev
   if (!e->diag_part) {
-    const int rc = device_alloc(&e->diag_part, (size_t)e->members * parts * kDiagFields, "the partials");
+    const int rc = device_alloc(&e->diag_part, (size_t)e->members * parts * kDiagFields, kWhere, "the partials");
     if (rc) return rc;
   }
   if (!e->diag_dev) {
-    const int rc = device_alloc(&e->diag_dev, (size_t)e->members * kDiagFields, "the reduced fields");
+    const int rc = device_alloc(&e->diag_dev, (size_t)e->members * kDiagFields, kWhere, "the reduced fields");
     if (rc) return rc;
   }
   EnsembleDiagArgs<T> a{};
@@ -70,24 +59,8 @@ int enqueue_ensemble_diag_t(nbx_ensemble* e, int first, int count) {
 extern "C" {
 
 int nbx_ensemble_diagnostics(nbx_ensemble* e, int32_t first, int32_t count, nbx_diag_t* out) {
-  return guarded("nbx_ensemble_diagnostics", [&]() -> int {
-  if (!e || !out) return fail(NBX_ERR_ARG, "nbx_ensemble_diagnostics: NULL argument");
-  if (first < 0 || count < 0 || (long long)first + count > e->members)
-    return fail(NBX_ERR_ARG, "nbx_ensemble_diagnostics: members [first, first + count) are outside [0, members)");
-  for (int k = 0; k < count; ++k)
-    if (out[k].struct_size != 0 && out[k].struct_size != (int32_t)sizeof(nbx_diag_t))
-      return fail(NBX_ERR_ARG, "nbx_ensemble_diagnostics: out[" + std::to_string(k) + "].struct_size does not match this library");
-  for (int k = first; k < first + count; ++k)
-    if (!e->uploaded[k]) return fail(NBX_ERR_STATE, "nbx_ensemble_diagnostics: member " + std::to_string(k) + " has not been uploaded");
-  if (count == 0) return NBX_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  const int rc = e->precision == 32 ? enqueue_ensemble_diag_t<float>(e, first, count) : enqueue_ensemble_diag_t<double>(e, first, count);
-  if (rc) return rc;
-  std::vector<double> raw((size_t)count * kDiagFields);
-  HIP_TRY(hipMemcpyAsync(raw.data(), e->diag_dev, sizeof(double) * raw.size(), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  for (int k = 0; k < count; ++k) diag_fill(raw.data() + (size_t)k * kDiagFields, e->n, e->steps_done, out + k);
-  return NBX_OK;
+  return batch_diagnostics<kDiagFields>(e, kWhere, first, count, out, [](auto t, nbx_ensemble* e, int first, int count) {
+    return enqueue_ensemble_diag_t<decltype(t)>(e, first, count);
   });
 }
 

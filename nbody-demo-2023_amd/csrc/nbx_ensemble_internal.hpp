@@ -1,39 +1,24 @@
 // nbx_ensemble_internal.hpp -- the ensemble object, shared by the translation units that serve it: nbx_ensemble.hip (create,
-// upload, step, download) and nbx_ensemble_diag.hip (diagnostics).  Not part of the C-ABI (include/nbx_ensemble.h is).
+// upload, step, download) and nbx_ensemble_diag.hip (diagnostics).  Not part of the C-ABI (include/nbx_ensemble.h is).  What an
+// ensemble has in common with a ragged ensemble -- most of its fields and all of its host plumbing -- is nbx_batch.hpp.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <vector>
-
 #include "../../include/nbx_ensemble.h"
-#include "nbx_internal.hpp"  // error plumbing; nbx_plan.hpp: nbx::EnsemblePlan
+#include "nbx_batch.hpp"  // nbx_detail::Batch; error plumbing; nbx_plan.hpp: nbx::EnsemblePlan
 
-struct nbx_ensemble {
-  int n = 0, members = 0, precision = 32, own_pad = 0;
+struct nbx_ensemble : nbx_detail::Batch {
+  static constexpr nbx_detail::BatchNames names{"nbx_ensemble", "ensemble"};
+  int n = 0, own_pad = 0;  // bodies per member; records between members in velm: n rounded up to the workgroup
+  size_t pos_stride = 0;   // records between members in posm: n_alloc + kSgprOverread
   nbx::EnsemblePlan plan;
   void (*launch_step)(nbx_ensemble*, double dt) = nullptr;  // plan.step, resolved by nbx_ensemble_create
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipDeviceProp_t prop{};
-  size_t rec = 16;         // bytes per {x,y,z,w} record
-  size_t pos_stride = 0;   // records between members in posm: n_alloc + kSgprOverread
-  void* posm[2] = {nullptr, nullptr};
-  int cur = 0;
-  void* velm = nullptr;
-  double* ke_part = nullptr;  // [members][grid_x]
-  bool have_parts = false;    // a step has written ke_part since the last upload
-  double* ke_dev = nullptr;   // [ke_cap] reduced sums (sum m v^2), slot s of member m at s * members + m
-  size_t ke_cap = 0;
-  std::vector<char> uploaded;  // per member
-  int uploaded_count = 0;
-  long long steps_done = 0;
-  bool profiling = false;
-  std::vector<hipEvent_t> ev;  // pairs start/stop
-  size_t ev_used = 0;
-  double step_ms_total = 0.0;
-  long long launches_timed = 0;
-  // diagnostics (nbx_ensemble_diag.hip): per-workgroup partials [members][parts][9] and the reduced fields [members][9],
-  // allocated on first use
-  double* diag_part = nullptr;
-  double* diag_dev = nullptr;
+  // ke_part is [members][plan.grid_x], diag_part [members][parts][9]
+  nbx_detail::MemberSpan layout(int k) const { return {(size_t)k * pos_stride, (size_t)k * (size_t)own_pad, n, plan.n_alloc}; }
 };
+static_assert(nbx::kTile == nbx::kBlock, "own_pad == plan.n_alloc: a member's velocity records end where the next member's begin");
+
+#pragma GCC visibility push(hidden)  // internal to libnbx.so, as nbx_batch.hpp
+namespace nbx_detail {
+// nbx_ensemble.hip: every member's partials -> ke_dev[slot * members + m], fixed order, on the ensemble's stream
+int enqueue_ke_reduce(nbx_ensemble* e, int slot);
+}  // namespace nbx_detail
+#pragma GCC visibility pop

@@ -10,44 +10,16 @@
 // trajectory, ke_part and have_parts do not see it.
 #include <hip/hip_runtime.h>
 
-#include <string>
-#include <vector>
-
 #include "../../include/nbx_ragged_diag.h"
 #include "nbx_ragged_diag_kernels.hpp"
-#include "nbx_ragged_internal.hpp"
+#include "nbx_ragged_internal.hpp"  // struct nbx_ragged; nbx_batch.hpp: batch_diagnostics, device_alloc, device_table
 
 using namespace nbx;
 using namespace nbx_detail;
 
-static_assert(kDiagFields == kDiagFieldCount, "diag_fill reads kDiagFieldCount raw sums per member");
-
 namespace {
 
-template <typename P>
-int device_alloc(P** p, size_t count, const char* what) {
-  const hipError_t err = hipMalloc(p, sizeof(P) * count);
-  if (err == hipSuccess) return NBX_OK;
-  *p = nullptr;
-  return fail(err == hipErrorOutOfMemory ? NBX_ERR_ALLOC : NBX_ERR_DEVICE,
-              std::string("nbx_ragged_diagnostics: hipMalloc of ") + what + ": " + hipGetErrorString(err));
-}
-
-// a host table (which lives in r->diag_plan as long as the object) -> a device copy, on the stream the launches follow on; *p is
-// set only once the copy has been enqueued
-template <typename P>
-int device_table(nbx_ragged* r, P** p, const std::vector<P>& src, const char* what) {
-  P* dev = nullptr;
-  const int rc = device_alloc(&dev, src.size(), what);
-  if (rc) return rc;
-  const hipError_t err = hipMemcpyAsync(dev, src.data(), sizeof(P) * src.size(), hipMemcpyHostToDevice, r->stream);
-  if (err != hipSuccess) {
-    (void)hipFree(dev);
-    return fail(NBX_ERR_DEVICE, std::string("nbx_ragged_diagnostics: copy of ") + what + ": " + hipGetErrorString(err));
-  }
-  *p = dev;
-  return NBX_OK;
-}
+constexpr const char* kWhere = "nbx_ragged_diagnostics";
 
 // first use: the plan, its two tables on the device, the partials and the reduced fields -- sizes fixed for the object's life
 int ensure_diag_buffers(nbx_ragged* r) {
@@ -57,10 +29,10 @@ int ensure_diag_buffers(nbx_ragged* r) {
   }
   const RaggedDiagPlan& d = r->diag_plan;
   int rc;
-  if (!r->diag_part && (rc = device_alloc(&r->diag_part, (size_t)d.total_rows * kDiagFields, "the partials"))) return rc;
-  if (!r->diag_dev && (rc = device_alloc(&r->diag_dev, (size_t)r->members * kDiagFields, "the reduced fields"))) return rc;
-  if (!r->diag_rows_dev && (rc = device_table(r, &r->diag_rows_dev, d.rows, "the members' row table"))) return rc;
-  if (!r->diag_work_dev && (rc = device_table(r, &r->diag_work_dev, d.work, "the work list"))) return rc;
+  if (!r->diag_part && (rc = device_alloc(&r->diag_part, (size_t)d.total_rows * kDiagFields, kWhere, "the partials"))) return rc;
+  if (!r->diag_dev && (rc = device_alloc(&r->diag_dev, (size_t)r->members * kDiagFields, kWhere, "the reduced fields"))) return rc;
+  if (!r->diag_rows_dev && (rc = device_table(r, &r->diag_rows_dev, d.rows, kWhere, "the members' row table"))) return rc;
+  if (!r->diag_work_dev && (rc = device_table(r, &r->diag_work_dev, d.work, kWhere, "the work list"))) return rc;
   return NBX_OK;
 }
 
@@ -91,25 +63,8 @@ int enqueue_ragged_diag_t(nbx_ragged* r, int first, int count) {
 extern "C" {
 
 int nbx_ragged_diagnostics(nbx_ragged* r, int32_t first, int32_t count, nbx_diag_t* out) {
-  return guarded("nbx_ragged_diagnostics", [&]() -> int {
-  if (!r || !out) return fail(NBX_ERR_ARG, "nbx_ragged_diagnostics: NULL argument");
-  if (first < 0 || count < 0 || (long long)first + count > r->members)
-    return fail(NBX_ERR_ARG, "nbx_ragged_diagnostics: members [first, first + count) are outside [0, members)");
-  for (int k = 0; k < count; ++k)
-    if (out[k].struct_size != 0 && out[k].struct_size != (int32_t)sizeof(nbx_diag_t))
-      return fail(NBX_ERR_ARG, "nbx_ragged_diagnostics: out[" + std::to_string(k) + "].struct_size does not match this library");
-  for (int k = first; k < first + count; ++k)
-    if (!r->uploaded[k]) return fail(NBX_ERR_STATE, "nbx_ragged_diagnostics: member " + std::to_string(k) + " has not been uploaded");
-  if (count == 0) return NBX_OK;
-  HIP_TRY(hipSetDevice(r->device));
-  const int rc = r->precision == 32 ? enqueue_ragged_diag_t<float>(r, first, count) : enqueue_ragged_diag_t<double>(r, first, count);
-  if (rc) return rc;
-  std::vector<double> raw((size_t)count * kDiagFields);
-  HIP_TRY(hipMemcpyAsync(raw.data(), r->diag_dev, sizeof(double) * raw.size(), hipMemcpyDeviceToHost, r->stream));
-  HIP_TRY(hipStreamSynchronize(r->stream));
-  for (int k = 0; k < count; ++k)
-    diag_fill(raw.data() + (size_t)k * kDiagFields, r->plan.member[(size_t)first + k].n, r->steps_done, out + k);
-  return NBX_OK;
+  return batch_diagnostics<kDiagFields>(r, kWhere, first, count, out, [](auto t, nbx_ragged* r, int first, int count) {
+    return enqueue_ragged_diag_t<decltype(t)>(r, first, count);
   });
 }
 

@@ -251,6 +251,18 @@ def initial_conditions(n, precision=32):
     return s
 
 
+def _opts(opts):
+    """An nbx_opts at its defaults (device -1: the current one) with the keyword options written over them."""
+    o = Opts()
+    o.struct_size = ctypes.sizeof(Opts)
+    o.device = -1
+    for k, v in opts.items():
+        if not hasattr(o, k):
+            raise TypeError("unknown nbx_opts field %r" % k)
+        setattr(o, k, v)
+    return o
+
+
 class Context:
     """One nbx_ctx.  Keyword options are the nbx_opts fields."""
 
@@ -259,13 +271,7 @@ class Context:
         self._h = ctypes.c_void_p()
         self.n = int(n)
         self.precision = int(precision)
-        o = Opts()
-        o.struct_size = ctypes.sizeof(Opts)
-        o.device = -1
-        for k, v in opts.items():
-            if not hasattr(o, k):
-                raise TypeError("unknown nbx_opts field %r" % k)
-            setattr(o, k, v)
+        o = _opts(opts)
         _check(self._L.nbx_create(ctypes.byref(self._h), self.n, self.precision, ctypes.byref(o)), "nbx_create")
         self.dtype = _dtype(self.precision)
 
@@ -354,30 +360,32 @@ class Context:
         return d.asdict()
 
 
-class Ensemble:
-    """One nbx_ensemble (include/nbx_ensemble.h): `members` independent systems of n bodies, one launch per time step for all
-    of them.  Keyword options are the nbx_opts fields an ensemble honours (device, bodies_per_lane, inner_loop)."""
+class _Batch:
+    """What Ensemble and Ragged share -- the library serves both from one host layer (csrc/nbx_batch.hpp), and every method here
+    is the C-ABI call of that name under the class's prefix.  A subclass sets members and precision, calls _create, and adds
+    upload and download, which differ in how the members' arrays are laid out."""
+    _prefix = None   # "nbx_ensemble": <prefix>_create, <prefix>_step, ...
+    _stats = None    # the ctypes mirror of <prefix>_stats_t
+    _what = None     # the entry points, as the "was built without ..." error names them
 
-    def __init__(self, n, members, precision=32, **opts):
+    def _call(self, name, *args):
+        where = "%s_%s" % (self._prefix, name)
+        _check(getattr(self._L, where)(self._h, *args), where)
+
+    def _create(self, opts, *args):
+        """<prefix>_create(&handle, *args, &nbx_opts) on a library that has this kind's entry points."""
         self._L = load()
-        if not hasattr(self._L, "nbx_ensemble_create"):
-            raise NbxError(NBX_ERR_STATE, "nbx_ensemble_create", "%s was built without the ensemble entry points" % LIB_PATH)
+        where = self._prefix + "_create"
+        if not hasattr(self._L, where):
+            raise NbxError(NBX_ERR_STATE, where, "%s was built without %s" % (LIB_PATH, self._what))
         self._h = ctypes.c_void_p()
-        self.n, self.members, self.precision = int(n), int(members), int(precision)
-        o = Opts()
-        o.struct_size = ctypes.sizeof(Opts)
-        o.device = -1
-        for k, v in opts.items():
-            if not hasattr(o, k):
-                raise TypeError("unknown nbx_opts field %r" % k)
-            setattr(o, k, v)
-        _check(self._L.nbx_ensemble_create(ctypes.byref(self._h), self.n, self.precision, self.members, ctypes.byref(o)),
-               "nbx_ensemble_create")
+        o = _opts(opts)
+        _check(getattr(self._L, where)(ctypes.byref(self._h), *args, ctypes.byref(o)), where)
         self.dtype = _dtype(self.precision)
 
     def close(self):
         if self._h:
-            self._L.nbx_ensemble_destroy(self._h)
+            getattr(self._L, self._prefix + "_destroy")(self._h)
             self._h = ctypes.c_void_p()
 
     def __enter__(self):
@@ -391,6 +399,52 @@ class Ensemble:
             self.close()
         except Exception:
             pass
+
+    def step(self, nsteps, dt=DT, kenergy=True):
+        """nsteps steps of every member; the kinetic energy of each member after the last one (array of `members`) if asked for."""
+        ke = np.zeros(self.members, dtype=np.float64) if kenergy else None
+        self._call("step", dt, nsteps, _ptr(ke))
+        return ke
+
+    def step_trace(self, nsteps, dt=DT):
+        """The kinetic energy of every member after every step: array (nsteps, members)."""
+        ke = np.zeros((max(nsteps, 1), self.members), dtype=np.float64)
+        self._call("step_trace", dt, nsteps, _ptr(ke))
+        return ke[:nsteps]
+
+    def sync(self):
+        self._call("sync")
+
+    def profile(self, enable=True):
+        self._call("profile", 1 if enable else 0)
+
+    def stats(self):
+        s = self._stats()
+        s.struct_size = ctypes.sizeof(s)
+        self._call("stats", ctypes.byref(s))
+        return s.asdict()
+
+    def diagnostics(self, first=0, count=None):
+        """<prefix>_diagnostics: one dict per member of [first, first + count) (default: all from `first`).  Synchronises."""
+        where = self._prefix + "_diagnostics"
+        if not hasattr(self._L, where):
+            raise NbxError(NBX_ERR_STATE, where, "%s was built without %s" % (LIB_PATH, where))
+        count = self.members - first if count is None else count
+        d = (Diag * max(count, 1))()
+        for k in range(max(count, 0)):
+            d[k].struct_size = ctypes.sizeof(Diag)
+        self._call("diagnostics", first, count, d)
+        return [d[k].asdict() for k in range(max(count, 0))]
+
+
+class Ensemble(_Batch):
+    """One nbx_ensemble (include/nbx_ensemble.h): `members` independent systems of n bodies, one launch per time step for all
+    of them.  Keyword options are the nbx_opts fields an ensemble honours (device, bodies_per_lane, inner_loop)."""
+    _prefix, _stats, _what = "nbx_ensemble", EnsembleStats, "the ensemble entry points"
+
+    def __init__(self, n, members, precision=32, **opts):
+        self.n, self.members, self.precision = int(n), int(members), int(precision)
+        self._create(opts, self.n, self.precision, self.members)
 
     def upload(self, states, first=0):
         """Members first, first + 1, ...: a list of state dicts (what initial_conditions returns), or one dict of (count, n) arrays."""
@@ -401,90 +455,30 @@ class Ensemble:
         for a in arrs:
             if a.ndim != 2 or a.shape != (arrs[0].shape[0], self.n):
                 raise NbxError(NBX_ERR_ARG, "array", "expected shape (count, %d), got %r" % (self.n, a.shape))
-        _check(self._L.nbx_ensemble_upload(self._h, first, arrs[0].shape[0], *[_ptr(a) for a in arrs]), "nbx_ensemble_upload")
-
-    def step(self, nsteps, dt=DT, kenergy=True):
-        """nsteps steps of every member; the kinetic energy of each member after the last one (array of `members`) if asked for."""
-        ke = np.zeros(self.members, dtype=np.float64) if kenergy else None
-        _check(self._L.nbx_ensemble_step(self._h, dt, nsteps, _ptr(ke)), "nbx_ensemble_step")
-        return ke
-
-    def step_trace(self, nsteps, dt=DT):
-        """The kinetic energy of every member after every step: array (nsteps, members)."""
-        ke = np.zeros((max(nsteps, 1), self.members), dtype=np.float64)
-        _check(self._L.nbx_ensemble_step_trace(self._h, dt, nsteps, _ptr(ke)), "nbx_ensemble_step_trace")
-        return ke[:nsteps]
+        self._call("upload", first, arrs[0].shape[0], *[_ptr(a) for a in arrs])
 
     def download(self, first=0, count=None):
         count = self.members - first if count is None else count
         out = {f: np.zeros((max(count, 0), self.n), dtype=self.dtype) for f in FIELDS[:6]}
-        _check(self._L.nbx_ensemble_download(self._h, first, count, *[_ptr(out[f]) for f in FIELDS[:6]]), "nbx_ensemble_download")
+        self._call("download", first, count, *[_ptr(out[f]) for f in FIELDS[:6]])
         return out
-
-    def sync(self):
-        _check(self._L.nbx_ensemble_sync(self._h), "nbx_ensemble_sync")
-
-    def profile(self, enable=True):
-        _check(self._L.nbx_ensemble_profile(self._h, 1 if enable else 0), "nbx_ensemble_profile")
-
-    def stats(self):
-        s = EnsembleStats()
-        s.struct_size = ctypes.sizeof(EnsembleStats)
-        _check(self._L.nbx_ensemble_stats(self._h, ctypes.byref(s)), "nbx_ensemble_stats")
-        return s.asdict()
 
     def diagnostics(self, first=0, count=None):
         """nbx_ensemble_diagnostics: one dict per member of [first, first + count) (default: all from `first`), each what
         Context.diagnostics() returns for a context of n bodies holding that member's state -- the same bits; one launch for
         all of them.  Synchronises."""
-        if not hasattr(self._L, "nbx_ensemble_diagnostics"):
-            raise NbxError(NBX_ERR_STATE, "nbx_ensemble_diagnostics", "%s was built without nbx_ensemble_diagnostics" % LIB_PATH)
-        count = self.members - first if count is None else count
-        d = (Diag * max(count, 1))()
-        for k in range(max(count, 0)):
-            d[k].struct_size = ctypes.sizeof(Diag)
-        _check(self._L.nbx_ensemble_diagnostics(self._h, first, count, d), "nbx_ensemble_diagnostics")
-        return [d[k].asdict() for k in range(max(count, 0))]
+        return super().diagnostics(first, count)
 
 
-class Ragged:
+class Ragged(_Batch):
     """One nbx_ragged (include/nbx_ragged.h): independent systems of different size, member k of sizes[k] bodies, one launch per
     time step for all of them.  Keyword options are the nbx_opts fields it honours (device, bodies_per_lane, inner_loop)."""
+    _prefix, _stats, _what = "nbx_ragged", RaggedStats, "the ragged-ensemble entry points"
 
     def __init__(self, sizes, precision=32, **opts):
-        self._L = load()
-        if not hasattr(self._L, "nbx_ragged_create"):
-            raise NbxError(NBX_ERR_STATE, "nbx_ragged_create", "%s was built without the ragged-ensemble entry points" % LIB_PATH)
-        self._h = ctypes.c_void_p()
         self.sizes = [int(n) for n in sizes]
         self.members, self.precision = len(self.sizes), int(precision)
-        o = Opts()
-        o.struct_size = ctypes.sizeof(Opts)
-        o.device = -1
-        for k, v in opts.items():
-            if not hasattr(o, k):
-                raise TypeError("unknown nbx_opts field %r" % k)
-            setattr(o, k, v)
-        n = (ctypes.c_int32 * max(self.members, 1))(*self.sizes)
-        _check(self._L.nbx_ragged_create(ctypes.byref(self._h), self.members, n, self.precision, ctypes.byref(o)), "nbx_ragged_create")
-        self.dtype = _dtype(self.precision)
-
-    def close(self):
-        if self._h:
-            self._L.nbx_ragged_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(opts, self.members, (ctypes.c_int32 * max(self.members, 1))(*self.sizes), self.precision)
 
     def _range(self, first, count):
         """The sizes of members [first, first + count), or [] where the range leaves [0, members) (the library names the error)."""
@@ -500,53 +494,22 @@ class Ragged:
                     raise NbxError(NBX_ERR_ARG, "array", "member %d: expected shape (%d,), got %r" % (first + k, n, np.shape(states[k][f])))
         arrs = [np.ascontiguousarray(np.concatenate([np.asarray(s[f], dtype=self.dtype) for s in states]) if states
                                      else np.zeros(0, dtype=self.dtype)) for f in FIELDS]
-        _check(self._L.nbx_ragged_upload(self._h, first, len(states), *[_ptr(a) for a in arrs]), "nbx_ragged_upload")
-
-    def step(self, nsteps, dt=DT, kenergy=True):
-        """nsteps steps of every member; the kinetic energy of each member after the last one (array of `members`) if asked for."""
-        ke = np.zeros(self.members, dtype=np.float64) if kenergy else None
-        _check(self._L.nbx_ragged_step(self._h, dt, nsteps, _ptr(ke)), "nbx_ragged_step")
-        return ke
-
-    def step_trace(self, nsteps, dt=DT):
-        """The kinetic energy of every member after every step: array (nsteps, members)."""
-        ke = np.zeros((max(nsteps, 1), self.members), dtype=np.float64)
-        _check(self._L.nbx_ragged_step_trace(self._h, dt, nsteps, _ptr(ke)), "nbx_ragged_step_trace")
-        return ke[:nsteps]
+        self._call("upload", first, len(states), *[_ptr(a) for a in arrs])
 
     def download(self, first=0, count=None):
         """Members [first, first + count) (default: all from `first`): a list of dicts of six arrays, one per member."""
         count = self.members - first if count is None else count
         sizes = self._range(first, count)
         flat = {f: np.zeros(max(sum(sizes), 1), dtype=self.dtype) for f in FIELDS[:6]}
-        _check(self._L.nbx_ragged_download(self._h, first, count, *[_ptr(flat[f]) for f in FIELDS[:6]]), "nbx_ragged_download")
+        self._call("download", first, count, *[_ptr(flat[f]) for f in FIELDS[:6]])
         at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
         return [{f: flat[f][at[k]:at[k + 1]].copy() for f in FIELDS[:6]} for k in range(len(sizes))]
-
-    def sync(self):
-        _check(self._L.nbx_ragged_sync(self._h), "nbx_ragged_sync")
-
-    def profile(self, enable=True):
-        _check(self._L.nbx_ragged_profile(self._h, 1 if enable else 0), "nbx_ragged_profile")
-
-    def stats(self):
-        s = RaggedStats()
-        s.struct_size = ctypes.sizeof(RaggedStats)
-        _check(self._L.nbx_ragged_stats(self._h, ctypes.byref(s)), "nbx_ragged_stats")
-        return s.asdict()
 
     def diagnostics(self, first=0, count=None):
         """nbx_ragged_diagnostics: one dict per member of [first, first + count) (default: all from `first`), each what
         Context.diagnostics() returns for a context of sizes[k] bodies holding that member's state -- the same bits; one launch
         for all of them.  Synchronises."""
-        if not hasattr(self._L, "nbx_ragged_diagnostics"):
-            raise NbxError(NBX_ERR_STATE, "nbx_ragged_diagnostics", "%s was built without nbx_ragged_diagnostics" % LIB_PATH)
-        count = self.members - first if count is None else count
-        d = (Diag * max(count, 1))()
-        for k in range(max(count, 0)):
-            d[k].struct_size = ctypes.sizeof(Diag)
-        _check(self._L.nbx_ragged_diagnostics(self._h, first, count, d), "nbx_ragged_diagnostics")
-        return [d[k].asdict() for k in range(max(count, 0))]
+        return super().diagnostics(first, count)
 
 
 class Group:

@@ -100,6 +100,8 @@ def test_the_build_files_compile_and_link_the_translation_unit():
     mk = open(os.path.join(ROOT, "Makefile")).read()
     assert re.search(r"^\$\(PKG\)/libnbx\.so:.*\$\(PKG\)/nbx_ensemble_diag\.o", mk, re.M)
     assert re.search(r"^\$\(PKG\)/nbx_ensemble_diag\.o: \$\(CSRC\)/nbx_ensemble_diag\.hip", mk, re.M)
+    for unit in ("nbx_ensemble", "nbx_ensemble_diag"):  # both include the host layer shared with ragged ensembles
+        assert re.search(r"^\$\(PKG\)/%s\.o:.*\$\(CSRC\)/nbx_ensemble_internal\.hpp.*\$\(CSRC\)/nbx_batch\.hpp" % unit, mk, re.M), unit
     sh = open(os.path.join(ROOT, "tools", "build_variant.sh")).read()
     assert "-c nbx_ensemble_diag.hip" in sh and "include/nbx_ensemble_diag.h" in sh
 

@@ -176,6 +176,8 @@ def test_the_build_files_compile_and_link_the_translation_unit():
                 "include/nbx_ragged.h", "include/nbx_ragged_diag.h"):
         assert dep in rule.group(1), dep
     assert re.search(r"^\$\(PKG\)/nbx_ragged\.o:.*nbx_ragged_internal\.hpp", mk, re.M)
+    for unit in ("nbx_ragged", "nbx_ragged_diag"):  # both include the host layer shared with ensembles
+        assert re.search(r"^\$\(PKG\)/%s\.o:.*\$\(CSRC\)/nbx_batch\.hpp" % unit, mk, re.M), unit
     sh = open(os.path.join(ROOT, "tools", "build_variant.sh")).read()
     for word in ("-c nbx_ragged.hip", "-c nbx_ragged_diag.hip", "include/nbx_ragged.h", "include/nbx_ragged_diag.h"):
         assert word in sh, word
