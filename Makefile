@@ -9,19 +9,19 @@ all: lib host oracle
 
 lib: $(PKG)/libnbx.so
 
-$(PKG)/nbx_api.o: $(CSRC)/nbx_api.hip $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_kernels.hpp $(CSRC)/nbx_jlane.hpp $(CSRC)/nbx_pair.hpp $(CSRC)/nbx_sgpr_loop.inc $(CSRC)/nbx_jlane_loop.inc include/nbx.h include/nbx_diag.h
+$(PKG)/nbx_api.o: $(CSRC)/nbx_api.hip $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_kernels.hpp $(CSRC)/nbx_jlane.hpp $(CSRC)/nbx_pair.hpp $(CSRC)/nbx_sgpr_loop.inc $(CSRC)/nbx_jlane_loop.inc include/nbx.h include/nbx_diag.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_group.o: $(CSRC)/nbx_group.hip $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_watchdog.hpp include/nbx.h include/nbx_diag.h
+$(PKG)/nbx_group.o: $(CSRC)/nbx_group.hip $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_watchdog.hpp include/nbx.h include/nbx_diag.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_diag.o: $(CSRC)/nbx_diag.hip $(CSRC)/nbx_diag_kernels.hpp $(CSRC)/nbx_diag_body.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h
+$(PKG)/nbx_diag.o: $(CSRC)/nbx_diag.hip $(CSRC)/nbx_diag_kernels.hpp $(CSRC)/nbx_diag_body.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_ensemble.o: $(CSRC)/nbx_ensemble.hip $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_ensemble_kernels.hpp $(CSRC)/nbx_jlane.hpp $(CSRC)/nbx_jlane_loop.inc $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h
+$(PKG)/nbx_ensemble.o: $(CSRC)/nbx_ensemble.hip $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_ensemble_kernels.hpp $(CSRC)/nbx_jlane.hpp $(CSRC)/nbx_jlane_loop.inc $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_ensemble_diag.o: $(CSRC)/nbx_ensemble_diag.hip $(CSRC)/nbx_ensemble_diag_kernels.hpp $(CSRC)/nbx_diag_body.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ensemble_diag.h
+$(PKG)/nbx_ensemble_diag.o: $(CSRC)/nbx_ensemble_diag.hip $(CSRC)/nbx_ensemble_diag_kernels.hpp $(CSRC)/nbx_diag_body.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ensemble_diag.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_ragged.o: $(CSRC)/nbx_ragged.hip $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_ragged_kernels.hpp $(CSRC)/nbx_jlane.hpp $(CSRC)/nbx_jlane_loop.inc $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ragged.h
+$(PKG)/nbx_ragged.o: $(CSRC)/nbx_ragged.hip $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_ragged_kernels.hpp $(CSRC)/nbx_jlane.hpp $(CSRC)/nbx_jlane_loop.inc $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ragged.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_ragged_diag.o: $(CSRC)/nbx_ragged_diag.hip $(CSRC)/nbx_ragged_diag_kernels.hpp $(CSRC)/nbx_diag_body.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ragged.h include/nbx_ragged_diag.h
+$(PKG)/nbx_ragged_diag.o: $(CSRC)/nbx_ragged_diag.hip $(CSRC)/nbx_ragged_diag_kernels.hpp $(CSRC)/nbx_diag_body.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ragged.h include/nbx_ragged_diag.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(PKG)/nbx_ic.o: $(CSRC)/nbx_ic.cpp include/nbx.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -Wall -ffp-contract=off -c $< -o $@

@@ -4,16 +4,16 @@
 // (ver7/GSimulation.cpp:138-200): it owns bodies [i_begin, i_begin+i_count), keeps
 // {x,y,z,G*m} of ALL bodies resident (double buffered) and {vx,vy,vz,m} of its own.
 // No CPU fallback exists: without a HIP device every entry point fails with NBX_ERR_DEVICE.
+// What a context shares with the batch objects on the host -- device choice, the energy trace and its read-back, profiling and
+// the event bracket, the shared part of create and destroy -- is nbx_object.hpp's; here are the kernel dispatch, graph replay,
+// the slice and exchange protocol, and upload / download over a slice.
 #include <hip/hip_runtime.h>
-
 
 #include <algorithm>
 #include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
-#include <new>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -33,8 +33,6 @@ std::string& last_error() {
 }  // namespace nbx_detail
 
 namespace {
-
-constexpr int kMaxProfiledLaunches = 8192;
 
 // ------------------------------------------------------------------------------------------
 // kernel dispatch: one launcher per entry of kInstances (nbx_plan.hpp) -- the only kernel instances this library compiles
@@ -85,16 +83,8 @@ int enqueue_force(nbx_ctx* c, bool accel, double dt) {
     hipLaunchKernelGGL(pair_transpose_kernel, dim3(ceil_div(npairs, kBlock)), dim3(kBlock), 0, c->stream, (const float4*)c->posm[c->cur],
                        (float4*)c->posm_pairs, npairs);
   }
-  // the exact kernel (validation) is not timed
-  const bool prof = c->profiling && c->plan.step.kind != INST_EXACT && c->ev_used + 2 <= c->ev.size();
-  if (prof) HIP_TRY(hipEventRecord(c->ev[c->ev_used], c->stream));
-  (accel ? c->launch_accel : c->launch_step)(c, dt, accel ? 1 : 0);
-  if (prof) {
-    HIP_TRY(hipEventRecord(c->ev[c->ev_used + 1], c->stream));
-    c->ev_used += 2;
-  }
-  HIP_TRY(hipGetLastError());
-  return NBX_OK;
+  // the force launch alone is timed, and the exact kernel (validation) is not
+  return timed_launch(c, c->plan.step.kind != INST_EXACT, [&] { (accel ? c->launch_accel : c->launch_step)(c, dt, accel ? 1 : 0); });
 }
 
 // energy partials one step of this context's shape writes: one per workgroup of the kernel that integrates
@@ -150,44 +140,17 @@ int graph_unit_exec(nbx_ctx* c, int unit, double dt, hipGraphExec_t* out) {
   return NBX_OK;
 }
 
-int ensure_ke_cap(nbx_ctx* c, int need) {
-  if (need <= c->ke_cap) return NBX_OK;
-  if (c->ke_dev) HIP_TRY(hipFree(c->ke_dev));
-  c->ke_dev = nullptr;
-  c->ke_cap = 0;
-  HIP_TRY(hipMalloc(&c->ke_dev, sizeof(double) * (size_t)need));
-  c->ke_cap = need;
-  return NBX_OK;
-}
-
 }  // namespace
+
 int nbx_detail::enqueue_ke_reduce(nbx_ctx* c, int slot) {
   hipLaunchKernelGGL(ke_reduce_kernel, dim3(1), dim3(kBlock), 0, c->stream, (const double*)c->ke_part,
                      c->ke_parts, c->ke_dev + slot);
   HIP_TRY(hipGetLastError());
   return NBX_OK;
 }
-namespace {
-
-int drain_profile(nbx_ctx* c) {
-  for (size_t k = 0; k + 1 < c->ev_used; k += 2) {
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[k], c->ev[k + 1]));
-    c->force_ms_total += ms;
-    c->force_timed += 1;
-  }
-  c->ev_used = 0;
-  return NBX_OK;
-}
-
-}  // namespace
 // the tuner's predictor: nbx_plan.hpp, force_cost
 double nbx_detail::model_force_cost(const nbx_ctx* c, int own) { return force_cost(c->plan, c->precision, c->prop.multiProcessorCount, own); }
 
-int nbx_detail::use_device(nbx_ctx* c) {
-  HIP_TRY(hipSetDevice(c->device));
-  return NBX_OK;
-}
 namespace {
 
 template <typename T>
@@ -272,61 +235,29 @@ const char* nbx_last_error(void) { return last_error().c_str(); }
 int32_t nbx_abi_version(void) { return NBX_ABI_VERSION; }
 
 int nbx_create(nbx_ctx** out, int32_t n, int32_t precision, const nbx_opts* opts) {
-  return guarded("nbx_create", [&]() -> int {
+  constexpr const char* where = "nbx_create";
+  return guarded(where, [&]() -> int {
+  // n and precision are looked at before the options: the order the errors of a call that has several are reported in
   if (!out) return fail(NBX_ERR_ARG, "nbx_create: out is NULL");
   *out = nullptr;
   if (n <= 0) return fail(NBX_ERR_ARG, "nbx_create: n must be > 0");
   if (precision != 32 && precision != 64) return fail(NBX_ERR_ARG, "nbx_create: precision must be 32 or 64");
   nbx_opts o;
-  std::memset(&o, 0, sizeof(o));
-  o.device = -1;
-  if (opts) {
-    if (opts->struct_size != 0 && opts->struct_size != (int32_t)sizeof(nbx_opts))
-      return fail(NBX_ERR_ARG, "nbx_create: nbx_opts.struct_size does not match this library");
-    o = *opts;
-  }
+  int rc = create_opts(where, out, opts, &o);
+  if (rc) return rc;
   if (o.i_begin < 0 || o.i_count < 0 || o.i_begin >= n || (long long)o.i_begin + o.i_count > n)
     return fail(NBX_ERR_ARG, "nbx_create: slice [i_begin, i_begin+i_count) is outside [0, n)");
   if (o.n_alloc != 0 && o.n_alloc < n) return fail(NBX_ERR_ARG, "nbx_create: n_alloc < n");
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(NBX_ERR_DEVICE, "nbx_create: no HIP device available (libnbx has no CPU path)");
-  int dev = o.device;
-  if (dev < 0) {
-    if (hipGetDevice(&dev) != hipSuccess) return fail(NBX_ERR_DEVICE, "nbx_create: hipGetDevice failed");
-  }
-  if (dev >= ndev) return fail(NBX_ERR_ARG, "nbx_create: device ordinal out of range");
-
-  nbx_ctx* c = new (std::nothrow) nbx_ctx();
-  if (!c) return fail(NBX_ERR_ALLOC, "nbx_create: out of host memory");
-  struct Owner { nbx_ctx* c; ~Owner() { nbx_destroy(c); } } owner{c};  // every failure path below frees the context
-  c->device = dev;
+  BatchOwner<nbx_ctx> owner{nbx_destroy};  // every failure path below frees the context
+  rc = batch_open(where, o, precision, &owner);
+  if (rc) return rc;
+  nbx_ctx* c = owner.o;
   c->n = n;
-  c->precision = precision;
-  c->rec = precision == 32 ? sizeof(float4) : sizeof(double4);
   c->i_begin = o.i_begin;
   c->i_count = o.i_count == 0 ? n - o.i_begin : o.i_count;
   c->n_alloc = round_up(std::max(n, o.n_alloc), kTile);
   c->own_pad = round_up(c->i_count, kBlock);
-
-#define CREATE_TRY(expr)                                                                 \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess) {                                                              \
-      std::string m_ = std::string("nbx_create: " #expr ": ") + hipGetErrorString(e_);   \
-      return fail(e_ == hipErrorOutOfMemory ? NBX_ERR_ALLOC : NBX_ERR_DEVICE, m_);       \
-    }                                                                                    \
-  } while (0)
-
-  CREATE_TRY(hipSetDevice(dev));
-  CREATE_TRY(hipGetDeviceProperties(&c->prop, dev));
-  if (o.external_stream) {
-    c->stream = (hipStream_t)o.stream;  // may be NULL: the default stream
-  } else {
-    CREATE_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    c->own_stream = true;
-  }
   const char* msg = nullptr;
   if (plan_launch({n, c->n_alloc, c->i_count, precision, c->prop.multiProcessorCount, c->own_stream}, o, &c->plan, &msg) != NBX_OK)
     return fail(NBX_ERR_ARG, msg);
@@ -342,25 +273,24 @@ int nbx_create(nbx_ctx** out, int32_t n, int32_t precision, const nbx_opts* opts
 
   // + spare records: the pipelined SGPR loop requests one batch past the last split (never used)
   const size_t pos_bytes = c->rec * (size_t)(c->n_alloc + kSgprOverread);
-  CREATE_TRY(hipMalloc(&c->posm[0], pos_bytes));
-  CREATE_TRY(hipMalloc(&c->posm[1], pos_bytes));
-  CREATE_TRY(hipMalloc(&c->velm, c->rec * (size_t)c->own_pad));
-  CREATE_TRY(hipMalloc(&c->accp, c->rec * (size_t)c->own_pad * c->plan.S));
+  CREATE_TRY(where, hipMalloc(&c->posm[0], pos_bytes));
+  CREATE_TRY(where, hipMalloc(&c->posm[1], pos_bytes));
+  CREATE_TRY(where, hipMalloc(&c->velm, c->rec * (size_t)c->own_pad));
+  CREATE_TRY(where, hipMalloc(&c->accp, c->rec * (size_t)c->own_pad * c->plan.S));
   const int max_parts = std::max(ceil_div(c->i_count, kBlock), c->plan.grid_x);
-  CREATE_TRY(hipMalloc(&c->ke_part, sizeof(double) * (size_t)max_parts));
-  if (c->plan.variant == NBX_KERNEL_EXACT || c->plan.variant == NBX_KERNEL_EXACT_FMA) CREATE_TRY(hipMalloc(&c->mass_all, (c->rec / 4) * (size_t)c->n_alloc));
+  CREATE_TRY(where, hipMalloc(&c->ke_part, sizeof(double) * (size_t)max_parts));
+  if (c->plan.variant == NBX_KERNEL_EXACT || c->plan.variant == NBX_KERNEL_EXACT_FMA) CREATE_TRY(where, hipMalloc(&c->mass_all, (c->rec / 4) * (size_t)c->n_alloc));
   if (c->plan.pairs) {  // same size and the same zero-filled spare records as posm
-    CREATE_TRY(hipMalloc(&c->posm_pairs, pos_bytes));
-    CREATE_TRY(hipMemsetAsync(c->posm_pairs, 0, pos_bytes, c->stream));
+    CREATE_TRY(where, hipMalloc(&c->posm_pairs, pos_bytes));
+    CREATE_TRY(where, hipMemsetAsync(c->posm_pairs, 0, pos_bytes, c->stream));
   }
-  CREATE_TRY(hipMemsetAsync(c->posm[0], 0, pos_bytes, c->stream));
-  CREATE_TRY(hipMemsetAsync(c->posm[1], 0, pos_bytes, c->stream));
-  CREATE_TRY(hipMemsetAsync(c->ke_part, 0, sizeof(double) * (size_t)max_parts, c->stream));
-  CREATE_TRY(hipStreamSynchronize(c->stream));
-#undef CREATE_TRY
-  if (ensure_ke_cap(c, 64) != NBX_OK) return NBX_ERR_ALLOC;  // message set by ensure_ke_cap
-  owner.c = nullptr;
-  *out = c;
+  CREATE_TRY(where, hipMemsetAsync(c->posm[0], 0, pos_bytes, c->stream));
+  CREATE_TRY(where, hipMemsetAsync(c->posm[1], 0, pos_bytes, c->stream));
+  CREATE_TRY(where, hipMemsetAsync(c->ke_part, 0, sizeof(double) * (size_t)max_parts, c->stream));
+  CREATE_TRY(where, hipStreamSynchronize(c->stream));
+  rc = ensure_ke_cap(c, where, 64);
+  if (rc) return rc;
+  *out = owner.release();
   last_error().clear();
   return NBX_OK;
   });
@@ -368,21 +298,11 @@ int nbx_create(nbx_ctx** out, int32_t n, int32_t precision, const nbx_opts* opts
 
 void nbx_destroy(nbx_ctx* c) {
   if (!c) return;
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);  // NULL = the default stream when the caller lent us that one
-  for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
+  batch_quiesce(c);
   for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
-  if (c->posm[0]) (void)hipFree(c->posm[0]);
-  if (c->posm[1]) (void)hipFree(c->posm[1]);
-  if (c->velm) (void)hipFree(c->velm);
-  if (c->accp) (void)hipFree(c->accp);
-  if (c->ke_part) (void)hipFree(c->ke_part);
-  if (c->mass_all) (void)hipFree(c->mass_all);
-  if (c->posm_pairs) (void)hipFree(c->posm_pairs);
-  if (c->ke_dev) (void)hipFree(c->ke_dev);
-  if (c->diag_part) (void)hipFree(c->diag_part);
-  if (c->diag_dev) (void)hipFree(c->diag_dev);
-  if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
+  for (void* p : {c->accp, c->mass_all, c->posm_pairs})
+    if (p) (void)hipFree(p);
+  batch_release(c);
   delete c;
 }
 
@@ -418,7 +338,7 @@ static int step_common(nbx_ctx* c, double dt, int32_t nsteps, double* ke_last, d
   int rc = use_device(c);
   if (rc) return rc;
   if (ke_trace) {
-    rc = ensure_ke_cap(c, std::max(nsteps, 1));
+    rc = ensure_ke_cap(c, "nbx_step", (size_t)std::max(nsteps, 1));
     if (rc) return rc;
   }
   int first = 0;
@@ -454,25 +374,7 @@ static int step_common(nbx_ctx* c, double dt, int32_t nsteps, double* ke_last, d
       if (rc) return rc;
     }
   }
-  if (ke_trace && nsteps > 0) {
-    HIP_TRY(hipMemcpyAsync(ke_trace, c->ke_dev, sizeof(double) * (size_t)nsteps, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int s = 0; s < nsteps; ++s) ke_trace[s] *= 0.5;  // ver7/GSimulation.cpp:200
-  } else if (ke_last) {
-    if (nsteps > 0 || c->ke_parts > 0) {
-      if (nsteps == 0) {
-        rc = enqueue_ke_reduce(c, 0);
-        if (rc) return rc;
-      }
-      double sum = 0.0;
-      HIP_TRY(hipMemcpyAsync(&sum, c->ke_dev, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      *ke_last = 0.5 * sum;
-    } else {
-      *ke_last = 0.0;
-    }
-  }
-  return NBX_OK;
+  return read_energies(c, 1, nsteps, c->ke_parts > 0, ke_last, ke_trace, [&] { return enqueue_ke_reduce(c, 0); });
   });
 }
 
@@ -551,15 +453,7 @@ int nbx_accel(nbx_ctx* c, void* ax, void* ay, void* az) {
   });
 }
 
-int nbx_sync(nbx_ctx* c) {
-  return guarded("nbx_sync", [&]() -> int {
-  if (!c) return fail(NBX_ERR_ARG, "nbx_sync: ctx is NULL");
-  int rc = use_device(c);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return NBX_OK;
-  });
-}
+int nbx_sync(nbx_ctx* c) { return batch_sync(c, "nbx_sync"); }
 
 int nbx_download(nbx_ctx* c, void* px, void* py, void* pz, void* vx, void* vy, void* vz) {
   return guarded("nbx_download", [&]() -> int {
@@ -573,30 +467,7 @@ int nbx_download(nbx_ctx* c, void* px, void* py, void* pz, void* vx, void* vy, v
   });
 }
 
-int nbx_profile(nbx_ctx* c, int32_t enable) {
-  return guarded("nbx_profile", [&]() -> int {
-  if (!c) return fail(NBX_ERR_ARG, "nbx_profile: ctx is NULL");
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (enable && c->ev.empty()) {
-    c->ev.resize(2 * kMaxProfiledLaunches);
-    for (auto& e : c->ev) e = nullptr;
-    for (auto& e : c->ev) HIP_TRY(hipEventCreate(&e));
-  }
-  if (!enable && c->profiling) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    rc = drain_profile(c);
-    if (rc) return rc;
-  }
-  if (enable && !c->profiling) {
-    c->force_ms_total = 0.0;
-    c->force_timed = 0;
-    c->ev_used = 0;
-  }
-  c->profiling = enable != 0;
-  return NBX_OK;
-  });
-}
+int nbx_profile(nbx_ctx* c, int32_t enable) { return batch_profile(c, "nbx_profile", enable); }
 
 int nbx_stats(nbx_ctx* c, nbx_stats_t* s) {
   return guarded("nbx_stats", [&]() -> int {
@@ -616,8 +487,8 @@ int nbx_stats(nbx_ctx* c, nbx_stats_t* s) {
   s->force_grid_x = p.grid_x; s->force_grid_y = p.grid_y; s->force_block = kBlock;
   s->cu_count = c->prop.multiProcessorCount; s->clock_mhz = c->prop.clockRate / 1000;
   s->steps_done = c->steps_done;
-  s->force_launches_timed = c->force_timed;
-  s->force_ms_total = c->force_ms_total;
+  s->force_launches_timed = c->launches_timed;
+  s->force_ms_total = c->ms_total;
   s->pairs_per_launch = (double)c->i_count * (double)c->n;
   s->graph_replays = c->graph_replays;
   s->use_graph = p.use_graph ? 1 : 0;

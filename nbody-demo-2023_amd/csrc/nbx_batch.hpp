@@ -1,6 +1,7 @@
 // nbx_batch.hpp -- the host side that ensembles (nbx_ensemble.hip, nbx_ensemble_diag.hip) and ragged ensembles (nbx_ragged.hip,
-// nbx_ragged_diag.hip) share: the fields both objects have, device choice, the energy trace, profiling, the member checks, the
-// step loop, the launcher table, upload and download over a member-layout lookup, create / destroy, and the diagnostics entry
+// nbx_ragged_diag.hip) share on top of what every device object has (nbx_object.hpp: the fields, device choice, the energy
+// trace, profiling, create / destroy -- the context, nbx_internal.hpp, stands on that base too): the member bookkeeping and
+// checks, the step loop, the launcher table, upload and download over a member-layout lookup, stats, and the diagnostics entry
 // point.  Host-only: it defines no kernel and includes no kernel header, so every translation unit keeps compiling exactly the
 // kernels it includes itself.
 //
@@ -10,30 +11,23 @@
 //   void (*launch_step)(Kind*, double dt);       one time step of all members, resolved at create from kLaunchers
 // and whose internal header declares the overload  int nbx_detail::enqueue_ke_reduce(Kind*, int slot)  (the step loop below
 // finds it by argument-dependent lookup); the kind's main translation unit defines it: it launches that unit's own reduce kernel.
-// The context (nbx_api.hip, nbx_group.hip) has helpers of the same names over nbx_ctx; its step path is tied to graph replay
-// and the exchange protocol and is not served from here.
+// The context's step path (nbx_api.hip) is tied to graph replay and the exchange protocol and is not served from here.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <array>
 #include <cstring>
-#include <new>
 #include <string>
 #include <utility>
 #include <vector>
 
-#include "nbx_internal.hpp"  // error plumbing, diag_fill; nbx_plan.hpp: kEnsembleInstances, kSgprOverread
+#include "nbx_internal.hpp"  // nbx_object.hpp: Object, error plumbing; diag_fill; nbx_plan.hpp: kEnsembleInstances, kSgprOverread
 #include "nbx_pair.hpp"      // the record types and the constants a record carries (inline code only, no kernel)
 
 // Nothing of this layer is visible outside the library: libnbx.so exports what the public headers declare, as before.
 #pragma GCC visibility push(hidden)
 namespace nbx_detail {
-
-struct BatchNames {
-  const char* prefix;  // "nbx_ensemble": the upload hint and the energy-trace text
-  const char* noun;    // "ensemble", as in "ensemble is NULL"
-};
 
 // Member k on the device: its first record in posm / velm, its bodies, and its records (n rounded up to the tile; kSgprOverread
 // spare records follow them in posm).
@@ -42,101 +36,13 @@ struct MemberSpan {
   int n, n_alloc;
 };
 
-struct Batch {
-  int members = 0, precision = 32;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipDeviceProp_t prop{};
-  size_t rec = 16;  // bytes per {x,y,z,w} record
-  void* posm[2] = {nullptr, nullptr};
-  int cur = 0;
-  void* velm = nullptr;
-  double* ke_part = nullptr;   // the step kernel's energy partials, a member's together
-  bool have_parts = false;     // a step has written ke_part since the last upload
-  double* ke_dev = nullptr;    // [ke_cap] reduced sums (sum m v^2), slot s of member m at s * members + m
-  size_t ke_cap = 0;
+struct Batch : Object {
+  int members = 0;
+  bool have_parts = false;     // a step has written ke_part (a member's partials together) since the last upload
   std::vector<char> uploaded;  // per member
   int uploaded_count = 0;
-  long long steps_done = 0;
-  bool profiling = false;
-  std::vector<hipEvent_t> ev;  // pairs start/stop
-  size_t ev_used = 0;
-  double step_ms_total = 0.0;
-  long long launches_timed = 0;
-  // diagnostics (nbx_*_diag.hip): per-workgroup partials [rows][9] and the reduced fields [members][9], allocated on first use
-  double* diag_part = nullptr;
-  double* diag_dev = nullptr;
+  // ke_dev: slot s of member m at s * members + m; diag_part is [rows][9], diag_dev [members][9]
 };
-
-constexpr int kMaxProfiledLaunches = 8192;
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// device selection, energy trace, profiling
-// ---------------------------------------------------------------------------------------------------------------------------
-inline int use_device(Batch* b) {
-  HIP_TRY(hipSetDevice(b->device));
-  return NBX_OK;
-}
-
-inline int ensure_ke_cap(Batch* b, const char* prefix, size_t need) {
-  if (need <= b->ke_cap) return NBX_OK;
-  if (b->ke_dev) HIP_TRY(hipFree(b->ke_dev));
-  b->ke_dev = nullptr;
-  b->ke_cap = 0;
-  hipError_t err = hipMalloc(&b->ke_dev, sizeof(double) * need);
-  if (err != hipSuccess)
-    return fail(err == hipErrorOutOfMemory ? NBX_ERR_ALLOC : NBX_ERR_DEVICE,
-                std::string(prefix) + ": hipMalloc of the energy trace: " + hipGetErrorString(err));
-  b->ke_cap = need;
-  return NBX_OK;
-}
-
-inline int drain_profile(Batch* b) {
-  for (size_t k = 0; k + 1 < b->ev_used; k += 2) {
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, b->ev[k], b->ev[k + 1]));
-    b->step_ms_total += ms;
-    b->launches_timed += 1;
-  }
-  b->ev_used = 0;
-  return NBX_OK;
-}
-
-template <typename O>
-int batch_sync(O* o, const char* where) {
-  return guarded(where, [&]() -> int {
-  if (!o) return fail(NBX_ERR_ARG, std::string(where) + ": " + O::names.noun + " is NULL");
-  int rc = use_device(o);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(o->stream));
-  return NBX_OK;
-  });
-}
-
-template <typename O>
-int batch_profile(O* o, const char* where, int32_t enable) {
-  return guarded(where, [&]() -> int {
-  if (!o) return fail(NBX_ERR_ARG, std::string(where) + ": " + O::names.noun + " is NULL");
-  int rc = use_device(o);
-  if (rc) return rc;
-  if (enable && o->ev.empty()) {
-    o->ev.assign(2 * kMaxProfiledLaunches, nullptr);
-    for (auto& ev : o->ev) HIP_TRY(hipEventCreate(&ev));
-  }
-  if (!enable && o->profiling) {
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    rc = drain_profile(o);
-    if (rc) return rc;
-  }
-  if (enable && !o->profiling) {
-    o->step_ms_total = 0.0;
-    o->launches_timed = 0;
-    o->ev_used = 0;
-  }
-  o->profiling = enable != 0;
-  return NBX_OK;
-  });
-}
 
 // *_stats up to the fields of the kind: the checks, the pending events drained, *s cleared and the fields every kind reports
 // filled in; `fill(s)` adds the rest.  S is the kind's public stats struct, named where + "_t".
@@ -156,7 +62,7 @@ int batch_stats(O* o, S* s, const char* where, Fill fill) {
   std::memset(s, 0, sizeof(*s));
   s->struct_size = (int32_t)sizeof(S);
   s->members = o->members; s->precision = o->precision; s->block = nbx::kBlock; s->cu_count = o->prop.multiProcessorCount;
-  s->steps_done = o->steps_done; s->launches_timed = o->launches_timed; s->step_ms_total = o->step_ms_total;
+  s->steps_done = o->steps_done; s->launches_timed = o->launches_timed; s->step_ms_total = o->ms_total;
   fill(s);
   return NBX_OK;
   });
@@ -184,17 +90,8 @@ inline void mark_uploaded(Batch* b, int first, int count) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// device buffers allocated after create (the diagnostics'); `where` is the entry point the text names
+// device tables made after create (the diagnostics'); `where` is the entry point the text names
 // ---------------------------------------------------------------------------------------------------------------------------
-template <typename P>
-int device_alloc(P** p, size_t count, const char* where, const char* what) {
-  const hipError_t err = hipMalloc(p, sizeof(P) * count);
-  if (err == hipSuccess) return NBX_OK;
-  *p = nullptr;
-  return fail(err == hipErrorOutOfMemory ? NBX_ERR_ALLOC : NBX_ERR_DEVICE,
-              std::string(where) + ": hipMalloc of " + what + ": " + hipGetErrorString(err));
-}
-
 // a host table (which lives as long as the object) -> a device copy, on the stream the launches follow on; *p is set only once
 // the copy has been enqueued
 template <typename P>
@@ -216,16 +113,9 @@ int device_table(Batch* b, P** p, const std::vector<P>& src, const char* where, 
 // ---------------------------------------------------------------------------------------------------------------------------
 template <typename O>
 int enqueue_step(O* o, double dt) {
-  const bool prof = o->profiling && o->ev_used + 2 <= o->ev.size();
-  if (prof) HIP_TRY(hipEventRecord(o->ev[o->ev_used], o->stream));
-  o->launch_step(o, dt);
-  if (prof) {
-    HIP_TRY(hipEventRecord(o->ev[o->ev_used + 1], o->stream));
-    o->ev_used += 2;
-  }
-  HIP_TRY(hipGetLastError());
-  o->have_parts = true;
-  return NBX_OK;
+  const int rc = timed_launch(o, true, [&] { o->launch_step(o, dt); });
+  if (rc == NBX_OK) o->have_parts = true;
+  return rc;
 }
 
 // *_step (ke_trace == nullptr) and, behind step_trace below, *_step_trace (ke_last == nullptr)
@@ -253,24 +143,7 @@ int step_common(O* o, const char* where, double dt, int32_t nsteps, double* ke_l
     else if (ke_last && s == nsteps - 1) rc = enqueue_ke_reduce(o, 0);
     if (rc) return rc;
   }
-  if (ke_trace && nsteps > 0) {
-    HIP_TRY(hipMemcpyAsync(ke_trace, o->ke_dev, sizeof(double) * S * (size_t)nsteps, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    for (size_t k = 0; k < S * (size_t)nsteps; ++k) ke_trace[k] *= 0.5;  // ver7/GSimulation.cpp:200
-  } else if (ke_last) {
-    if (nsteps > 0 || o->have_parts) {
-      if (nsteps == 0) {
-        rc = enqueue_ke_reduce(o, 0);
-        if (rc) return rc;
-      }
-      HIP_TRY(hipMemcpyAsync(ke_last, o->ke_dev, sizeof(double) * S, hipMemcpyDeviceToHost, o->stream));
-      HIP_TRY(hipStreamSynchronize(o->stream));
-      for (size_t m = 0; m < S; ++m) ke_last[m] *= 0.5;
-    } else {
-      for (size_t m = 0; m < S; ++m) ke_last[m] = 0.0;
-    }
-  }
-  return NBX_OK;
+  return read_energies(o, S, nsteps, o->have_parts, ke_last, ke_trace, [&] { return enqueue_ke_reduce(o, 0); });
   });
 }
 
@@ -411,66 +284,11 @@ int batch_download(O* o, const char* where, int32_t first, int32_t count, void* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// create and destroy.  A *_create is: create_opts, the kind's planning (every argument check before the first HIP call),
-// batch_open, planning again with the CU count, the kind's own buffers under CREATE_TRY, owner.release().
+// create (after batch_open of nbx_object.hpp)
 // ---------------------------------------------------------------------------------------------------------------------------
-#define CREATE_TRY(where, expr)                                                              \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      std::string m_ = std::string(where) + ": " #expr ": " + hipGetErrorString(e_);         \
-      return fail(e_ == hipErrorOutOfMemory ? NBX_ERR_ALLOC : NBX_ERR_DEVICE, m_);           \
-    }                                                                                        \
-  } while (0)
-
-// frees the object on every failure path of *_create
-template <typename O>
-struct BatchOwner {
-  void (*destroy)(O*);
-  O* o = nullptr;
-  ~BatchOwner() { if (o) destroy(o); }
-  O* release() { O* p = o; o = nullptr; return p; }
-};
-
-// *out cleared, the caller's options or the defaults -> *o
-template <typename O>
-int create_opts(const char* where, O** out, const nbx_opts* opts, nbx_opts* o) {
-  if (!out) return fail(NBX_ERR_ARG, std::string(where) + ": out is NULL");
-  *out = nullptr;
-  std::memset(o, 0, sizeof(*o));
-  o->device = -1;
-  if (opts) {
-    if (opts->struct_size != 0 && opts->struct_size != (int32_t)sizeof(nbx_opts))
-      return fail(NBX_ERR_ARG, std::string(where) + ": nbx_opts.struct_size does not match this library");
-    *o = *opts;
-  }
-  return NBX_OK;
-}
-
-// the device, the object (owned by *owner from here on) and its stream; prop.multiProcessorCount is known afterwards
-template <typename O>
-int batch_open(const char* where, const nbx_opts& o, int members, int precision, BatchOwner<O>* owner) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(NBX_ERR_DEVICE, std::string(where) + ": no HIP device available (libnbx has no CPU path)");
-  int dev = o.device;
-  if (dev < 0) {
-    if (hipGetDevice(&dev) != hipSuccess) return fail(NBX_ERR_DEVICE, std::string(where) + ": hipGetDevice failed");
-  }
-  if (dev >= ndev) return fail(NBX_ERR_ARG, std::string(where) + ": device ordinal out of range");
-
-  O* b = new (std::nothrow) O();
-  if (!b) return fail(NBX_ERR_ALLOC, std::string(where) + ": out of host memory");
-  owner->o = b;
-  b->device = dev;
+inline void set_members(Batch* b, int members) {
   b->members = members;
-  b->precision = precision;
-  b->rec = precision == 32 ? sizeof(float4) : sizeof(double4);
   b->uploaded.assign((size_t)members, 0);
-  CREATE_TRY(where, hipSetDevice(dev));
-  CREATE_TRY(where, hipGetDeviceProperties(&b->prop, dev));
-  CREATE_TRY(where, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-  return NBX_OK;
 }
 
 // plan.step -> o->launch_step
@@ -480,21 +298,6 @@ int resolve_launcher(O* o, const char* where) {
   if (k < 0) return fail(NBX_ERR_ARG, std::string(where) + ": no kernel instance for this bodies_per_lane / precision");
   o->launch_step = kLaunchers<O, Launch>[k];
   return NBX_OK;
-}
-
-// A *_destroy is: batch_quiesce, free what the kind owns, batch_release, delete.  The stream is synchronised first and
-// destroyed last.
-inline void batch_quiesce(Batch* b) {
-  (void)hipSetDevice(b->device);
-  if (b->stream) (void)hipStreamSynchronize(b->stream);
-}
-
-inline void batch_release(Batch* b) {
-  for (hipEvent_t ev : b->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  for (void* p : {b->posm[0], b->posm[1], b->velm, (void*)b->ke_part, (void*)b->ke_dev, (void*)b->diag_part, (void*)b->diag_dev})
-    if (p) (void)hipFree(p);
-  if (b->stream) (void)hipStreamDestroy(b->stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -21,15 +21,16 @@ static_assert(kDiagFields == kDiagFieldCount, "nbx_group.hip sizes the all-gathe
 namespace {
 
 template <typename T>
-int enqueue_diag_t(nbx_ctx* c) {
+int enqueue_diag_t(nbx_ctx* c, const char* where) {
   using T4 = typename V4<T>::type;
   constexpr int B = kDiagBodies<T>;
   const int blocks = ceil_div(c->i_count, kBlock * B);
   int splits = 1, per = 0;
   diag_splits(blocks, ceil_div(c->n, kTile), &splits, &per);
   const int parts = blocks * splits;  // i_count and n are fixed for the context's life: so is the size of diag_part
-  if (!c->diag_part) HIP_TRY(hipMalloc(&c->diag_part, sizeof(double) * kDiagFields * (size_t)parts));
-  if (!c->diag_dev) HIP_TRY(hipMalloc(&c->diag_dev, sizeof(double) * kDiagFields));
+  int rc = NBX_OK;
+  if (!c->diag_part && (rc = device_alloc(&c->diag_part, kDiagFields * (size_t)parts, where, "the partials"))) return rc;
+  if (!c->diag_dev && (rc = device_alloc(&c->diag_dev, (size_t)kDiagFields, where, "the reduced fields"))) return rc;
   hipLaunchKernelGGL((diag_kernel<T, B>), dim3(blocks, splits), dim3(kBlock), 0, c->stream, (const T4*)c->posm[c->cur],
                      (const T4*)c->velm, c->i_begin, c->i_count, c->n, per, c->diag_part);
   HIP_TRY(hipGetLastError());
@@ -45,7 +46,7 @@ int nbx_detail::enqueue_diagnostics(nbx_ctx* c, const char* where) {
   if (c->pending_commit) return fail(NBX_ERR_STATE, std::string(where) + ": a local step awaits nbx_commit");
   const int rc = use_device(c);
   if (rc) return rc;
-  return c->precision == 32 ? enqueue_diag_t<float>(c) : enqueue_diag_t<double>(c);
+  return c->precision == 32 ? enqueue_diag_t<float>(c, where) : enqueue_diag_t<double>(c, where);
 }
 
 void nbx_detail::diag_fill(const double* raw, int32_t i_count, int64_t steps_done, nbx_diag_t* out) {

@@ -1,7 +1,7 @@
 // nbx_ensemble.hip -- include/nbx_ensemble.h over the kernels of nbx_ensemble_kernels.hpp: S independent systems of n bodies,
 // one launch per time step for all of them.  The launch shape and the kernel instance come from plan_ensemble (nbx_plan.hpp);
 // this file instantiates exactly kEnsembleInstances and launches the one the plan names.  The host plumbing -- the step loop,
-// upload and download, profiling, the shared part of create and destroy -- is nbx_batch.hpp's; here are the kernel arguments,
+// upload and download, profiling, the shared part of create and destroy -- is nbx_batch.hpp's and, under it, nbx_object.hpp's; here are the kernel arguments,
 // the launches and what of create and stats belongs to an ensemble.
 //
 // Plain launches on the ensemble's own non-blocking stream, no graph capture: one launch per step costs the host 3-4 us, and
@@ -66,9 +66,10 @@ int nbx_ensemble_create(nbx_ensemble** out, int32_t n, int32_t precision, int32_
   if (plan_ensemble(n, precision, members, 0, o, &plan, &msg) != NBX_OK) return fail(NBX_ERR_ARG, msg);
 
   BatchOwner<nbx_ensemble> owner{nbx_ensemble_destroy};
-  rc = batch_open(where, o, members, precision, &owner);
+  rc = batch_open(where, o, precision, &owner);
   if (rc) return rc;
   nbx_ensemble* e = owner.o;
+  set_members(e, members);
   e->n = n;
   e->own_pad = round_up(n, kBlock);
   if (plan_ensemble(n, precision, members, e->prop.multiProcessorCount, o, &e->plan, &msg) != NBX_OK) return fail(NBX_ERR_ARG, msg);

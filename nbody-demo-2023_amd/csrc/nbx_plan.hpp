@@ -6,6 +6,7 @@
 // nbx_ragged_diagnostics.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cstddef>
 #include <cstdio>
 #include <numeric>
@@ -408,27 +409,25 @@ inline int plan_launch(const PlanInput& in, const nbx_opts& o, Plan* p, const ch
 // Ensembles (include/nbx_ensemble.h): `members` independent systems of n bodies advanced by one launch per step, grid
 // (workgroups per member, members).  Every member runs the jlane kernel body exactly as a context of that NB and loop does.
 // ---------------------------------------------------------------------------------------------------------------------------
-namespace instance_list {  // the ensemble_step_kernel instances nbx_ensemble.hip compiles: the jlane rows of kInstances
-constexpr Instance kEnsembleInstances[] = {
-    {J, 32, 2, 0, 0, 0, false, ASM}, {J, 32, 2, 0, 0, 0, false, CXX}, {J, 32, 4, 0, 0, 0, false, ASM}, {J, 32, 4, 0, 0, 0, false, CXX},
-    {J, 32, 8, 0, 0, 0, false, ASM}, {J, 32, 8, 0, 0, 0, false, CXX}, {J, 32, 16, 0, 0, 0, false, CXX},
-    {J, 64, 2, 0, 0, 0, false, CXX}, {J, 64, 4, 0, 0, 0, false, CXX}, {J, 64, 8, 0, 0, 0, false, CXX},
-};
-}  // namespace instance_list
-using instance_list::kEnsembleInstances;
-constexpr int kEnsembleInstanceCount = (int)(sizeof(kEnsembleInstances) / sizeof(kEnsembleInstances[0]));
+// The step-kernel instances nbx_ensemble.hip and nbx_ragged.hip compile: the jlane rows of kInstances in their order, so that a
+// member can run every shape a jlane context can, and no other.
+constexpr int kEnsembleInstanceCount = [] {
+  int rows = 0;
+  for (const Instance& k : kInstances) rows += k.kind == INST_JLANE;
+  return rows;
+}();
+constexpr auto kEnsembleInstances = [] {
+  std::array<Instance, kEnsembleInstanceCount> rows{};
+  int at = 0;
+  for (const Instance& k : kInstances)
+    if (k.kind == INST_JLANE) rows[at++] = k;
+  return rows;
+}();
 constexpr int ensemble_instance_index(const Instance& k) {
   for (int i = 0; i < kEnsembleInstanceCount; ++i)
     if (kEnsembleInstances[i] == k) return i;
   return -1;
 }
-constexpr bool ensemble_instances_mirror_the_jlane_rows() {
-  int rows = 0;
-  for (int i = 0; i < kInstanceCount; ++i)
-    if (kInstances[i].kind == INST_JLANE) { ++rows; if (ensemble_instance_index(kInstances[i]) < 0) return false; }
-  return rows == kEnsembleInstanceCount;
-}
-static_assert(ensemble_instances_mirror_the_jlane_rows(), "a member must be able to run every shape a jlane context can, and no other");
 
 constexpr int kEnsembleMaxMembers = 65535;  // gridDim.y
 
@@ -439,8 +438,38 @@ struct EnsemblePlan {
   Instance step{};
 };
 
-// nbx_ensemble_create's plan.  NBX_OK, or NBX_ERR_ARG with the text of nbx_last_error() in *msg.  Reads of `o`: bodies_per_lane,
-// inner_loop and the fields an ensemble cannot honour (which must be at their defaults).
+// Bodies per wave, inner loop and kernel instance of a launch whose members all run the jlane kernel body: the rule plan_ensemble
+// and plan_ragged share -- jlane_bodies_per_wave_of with the waves of all members counted, then the loop as for a context.
+// `waves_of(nb)` = the launch's waves with nb bodies each; `fn` = the entry point the texts name.  Fills p->NB, loop, D and step.
+template <typename P, typename WavesOf>
+inline int plan_wave_shape(WavesOf&& waves_of, int members, int precision, int cus, const nbx_opts& o, const char* fn, P* p, const char** msg) {
+  auto fail = [fn, msg](const char* text) {
+    static thread_local char buf[160];
+    std::snprintf(buf, sizeof buf, "%s: %s", fn, text);
+    *msg = buf;
+    return NBX_ERR_ARG;
+  };
+  const int max_nb = precision == 32 ? 16 : 8;
+  int NB = o.bodies_per_lane;
+  if (NB != 0 && ((NB != 2 && NB != 4 && NB != 8 && NB != 16) || NB > max_nb))
+    return fail("bodies_per_lane must be 0 (auto), 2, 4, 8 or -- fp32 only -- 16 bodies per wave");
+  if (o.inner_loop != NBX_LOOP_AUTO && o.inner_loop != NBX_LOOP_CXX && o.inner_loop != NBX_LOOP_ASM)
+    return fail("inner_loop must be NBX_LOOP_AUTO, NBX_LOOP_CXX or NBX_LOOP_ASM");
+  // the hand-scheduled loop asked for by name: the choice is among the shapes that have one (fp32: up to 8 bodies per wave)
+  if (NB == 0) NB = jlane_bodies_per_wave_of(waves_of, members, precision, cus, o.inner_loop == NBX_LOOP_ASM && precision == 32 ? 8 : 16);
+  const bool asm_loop_compiled = ensemble_instance_index({INST_JLANE, precision, NB, 0, 0, 0, false, LOOP_ASM}) >= 0;
+  int loop = (o.inner_loop != NBX_LOOP_CXX && asm_loop_compiled) ? LOOP_ASM : LOOP_CXX;
+  if (o.inner_loop == NBX_LOOP_ASM && loop != LOOP_ASM)
+    return fail("no hand-scheduled loop for this shape (needs fp32 and 2, 4 or 8 bodies per wave)");
+  if (o.inner_loop == NBX_LOOP_AUTO && loop == LOOP_ASM && !jlane_auto_takes_generated_loop(NB, waves_of(NB), cus)) loop = LOOP_CXX;
+  p->NB = NB; p->loop = loop; p->D = jlane_depth(precision, NB);
+  p->step = {INST_JLANE, precision, NB, 0, 0, 0, false, loop};
+  return NBX_OK;
+}
+
+// nbx_ensemble_create's plan.  NBX_OK, or NBX_ERR_ARG with the text of nbx_last_error() in *msg (which may point into a
+// thread-local buffer).  Reads of `o`: bodies_per_lane, inner_loop and the fields an ensemble cannot honour (which must be at
+// their defaults).
 inline int plan_ensemble(int n, int precision, int members, int cus, const nbx_opts& o, EnsemblePlan* p, const char** msg) {
   auto fail = [msg](const char* text) { *msg = text; return NBX_ERR_ARG; };
   *p = EnsemblePlan{};
@@ -461,24 +490,10 @@ inline int plan_ensemble(int n, int precision, int members, int cus, const nbx_o
   if (o.j_split > 1) return fail("nbx_ensemble_create: j_split must be 0 or 1 (a member's j range is not split over workgroups)");
   if (o.i_begin != 0 || o.i_count != 0) return fail("nbx_ensemble_create: i_begin and i_count must be 0 (an ensemble is not sharded; run one ensemble per GPU)");
   if (o.external_stream != 0) return fail("nbx_ensemble_create: external_stream must be 0 (an ensemble steps on a stream of its own)");
-  const int max_nb = precision == 32 ? 16 : 8;
-  int NB = o.bodies_per_lane;
-  if (NB != 0 && ((NB != 2 && NB != 4 && NB != 8 && NB != 16) || NB > max_nb))
-    return fail("nbx_ensemble_create: bodies_per_lane must be 0 (auto), 2, 4, 8 or -- fp32 only -- 16 bodies per wave");
-  if (o.inner_loop != NBX_LOOP_AUTO && o.inner_loop != NBX_LOOP_CXX && o.inner_loop != NBX_LOOP_ASM)
-    return fail("nbx_ensemble_create: inner_loop must be NBX_LOOP_AUTO, NBX_LOOP_CXX or NBX_LOOP_ASM");
-  // the hand-scheduled loop asked for by name: the choice is among the shapes that have one (fp32: up to 8 bodies per wave)
-  if (NB == 0) NB = jlane_bodies_per_wave(n, members, precision, cus, o.inner_loop == NBX_LOOP_ASM && precision == 32 ? 8 : 16);
-  const bool asm_loop_compiled = ensemble_instance_index({INST_JLANE, precision, NB, 0, 0, 0, false, LOOP_ASM}) >= 0;
-  int loop = (o.inner_loop != NBX_LOOP_CXX && asm_loop_compiled) ? LOOP_ASM : LOOP_CXX;
-  if (o.inner_loop == NBX_LOOP_ASM && loop != LOOP_ASM)
-    return fail("nbx_ensemble_create: no hand-scheduled loop for this shape (needs fp32 and 2, 4 or 8 bodies per wave)");
-  if (o.inner_loop == NBX_LOOP_AUTO && loop == LOOP_ASM && !jlane_auto_takes_generated_loop(NB, (long long)members * ceil_div(n, NB), cus))
-    loop = LOOP_CXX;
+  const int rc = plan_wave_shape([=](int nb) { return (long long)members * ceil_div(n, nb); }, members, precision, cus, o, "nbx_ensemble_create", p, msg);
+  if (rc) return rc;
   p->n_alloc = n_alloc;
-  p->NB = NB; p->loop = loop; p->D = jlane_depth(precision, NB);
-  p->grid_x = ceil_div(ceil_div(n, NB), 4); p->grid_y = members;
-  p->step = {INST_JLANE, precision, NB, 0, 0, 0, false, loop};
+  p->grid_x = ceil_div(ceil_div(n, p->NB), 4); p->grid_y = members;
   return NBX_OK;
 }
 
@@ -549,12 +564,6 @@ inline int plan_ragged(const int* n, int members, int precision, int cus, const 
   if (o.j_split > 1) return fail("nbx_ragged_create: j_split must be 0 or 1 (a member's j range is not split over workgroups)");
   if (o.i_begin != 0 || o.i_count != 0) return fail("nbx_ragged_create: i_begin and i_count must be 0 (a ragged ensemble is not sharded; run one per GPU)");
   if (o.external_stream != 0) return fail("nbx_ragged_create: external_stream must be 0 (a ragged ensemble steps on a stream of its own)");
-  const int max_nb = precision == 32 ? 16 : 8;
-  int NB = o.bodies_per_lane;
-  if (NB != 0 && ((NB != 2 && NB != 4 && NB != 8 && NB != 16) || NB > max_nb))
-    return fail("nbx_ragged_create: bodies_per_lane must be 0 (auto), 2, 4, 8 or -- fp32 only -- 16 bodies per wave");
-  if (o.inner_loop != NBX_LOOP_AUTO && o.inner_loop != NBX_LOOP_CXX && o.inner_loop != NBX_LOOP_ASM)
-    return fail("nbx_ragged_create: inner_loop must be NBX_LOOP_AUTO, NBX_LOOP_CXX or NBX_LOOP_ASM");
   // One NB and one loop for the whole launch (NB is a template argument): jlane_bodies_per_wave's rule with the waves of all
   // members counted.  That members differ in j length does not enter -- nobody has measured whether it matters;
   // scripts/ragged_sweep.py records the time of every NB next to the one taken here.
@@ -563,15 +572,10 @@ inline int plan_ragged(const int* n, int members, int precision, int cus, const 
     for (int k = 0; k < members; ++k) w += ceil_div(n[k], nb);
     return w;
   };
-  if (NB == 0) NB = jlane_bodies_per_wave_of(waves_of, members, precision, cus, o.inner_loop == NBX_LOOP_ASM && precision == 32 ? 8 : 16);
-  const bool asm_loop_compiled = ensemble_instance_index({INST_JLANE, precision, NB, 0, 0, 0, false, LOOP_ASM}) >= 0;
-  int loop = (o.inner_loop != NBX_LOOP_CXX && asm_loop_compiled) ? LOOP_ASM : LOOP_CXX;
-  if (o.inner_loop == NBX_LOOP_ASM && loop != LOOP_ASM)
-    return fail("nbx_ragged_create: no hand-scheduled loop for this shape (needs fp32 and 2, 4 or 8 bodies per wave)");
-  if (o.inner_loop == NBX_LOOP_AUTO && loop == LOOP_ASM && !jlane_auto_takes_generated_loop(NB, waves_of(NB), cus)) loop = LOOP_CXX;
+  const int rc = plan_wave_shape(waves_of, members, precision, cus, o, "nbx_ragged_create", p, msg);
+  if (rc) return rc;
+  const int NB = p->NB;
   p->members = members; p->precision = precision;
-  p->NB = NB; p->loop = loop; p->D = jlane_depth(precision, NB);
-  p->step = {INST_JLANE, precision, NB, 0, 0, 0, false, loop};
   // members one behind the other, in member order
   p->member.resize((size_t)members);
   p->n_min = p->n_max = n[0];

@@ -2,7 +2,7 @@
 // launch per time step for all of them.  The layout, the work list and the kernel instance come from plan_ragged
 // (nbx_plan.hpp); this file instantiates exactly kEnsembleInstances -- the shapes a jlane context can run -- as
 // ragged_step_kernel and launches the one the plan names.  The host plumbing -- the step loop, upload and download, profiling,
-// the shared part of create and destroy -- is nbx_batch.hpp's; here are the kernel arguments, the launches and what of create,
+// the shared part of create and destroy -- is nbx_batch.hpp's and, under it, nbx_object.hpp's; here are the kernel arguments, the launches and what of create,
 // destroy and stats belongs to a ragged ensemble.
 //
 // Plain launches on the object's own non-blocking stream, no graph capture, as for an ensemble (nbx_ensemble.hip).
@@ -69,9 +69,10 @@ int nbx_ragged_create(nbx_ragged** out, int32_t members, const int32_t* n, int32
   }
 
   BatchOwner<nbx_ragged> owner{nbx_ragged_destroy};
-  rc = batch_open(where, o, members, precision, &owner);
+  rc = batch_open(where, o, precision, &owner);
   if (rc) return rc;
   nbx_ragged* r = owner.o;
+  set_members(r, members);
   if (plan_ragged(n, members, precision, r->prop.multiProcessorCount, o, &r->plan, &msg) != NBX_OK) return fail(NBX_ERR_ARG, msg);
   rc = resolve_launcher<nbx_ragged, RaggedLaunch>(r, where);
   if (rc) return rc;

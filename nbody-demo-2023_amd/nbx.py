@@ -263,21 +263,18 @@ def _opts(opts):
     return o
 
 
-class Context:
-    """One nbx_ctx.  Keyword options are the nbx_opts fields."""
+class _Handle:
+    """A handle of the library and the entry point that destroys it: closed by close(), on leaving a `with` block, or with the
+    Python object.  A subclass names the entry point in _destroy and creates the handle into self._h."""
+    _destroy = None
 
-    def __init__(self, n, precision=32, **opts):
+    def _new_handle(self):
         self._L = load()
         self._h = ctypes.c_void_p()
-        self.n = int(n)
-        self.precision = int(precision)
-        o = _opts(opts)
-        _check(self._L.nbx_create(ctypes.byref(self._h), self.n, self.precision, ctypes.byref(o)), "nbx_create")
-        self.dtype = _dtype(self.precision)
 
     def close(self):
         if self._h:
-            self._L.nbx_destroy(self._h)
+            getattr(self._L, self._destroy)(self._h)
             self._h = ctypes.c_void_p()
 
     def __enter__(self):
@@ -291,6 +288,19 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+class Context(_Handle):
+    """One nbx_ctx.  Keyword options are the nbx_opts fields."""
+    _destroy = "nbx_destroy"
+
+    def __init__(self, n, precision=32, **opts):
+        self._new_handle()
+        self.n = int(n)
+        self.precision = int(precision)
+        o = _opts(opts)
+        _check(self._L.nbx_create(ctypes.byref(self._h), self.n, self.precision, ctypes.byref(o)), "nbx_create")
+        self.dtype = _dtype(self.precision)
 
     def _arr(self, a):
         a = np.ascontiguousarray(a, dtype=self.dtype)
@@ -360,7 +370,7 @@ class Context:
         return d.asdict()
 
 
-class _Batch:
+class _Batch(_Handle):
     """What Ensemble and Ragged share -- the library serves both from one host layer (csrc/nbx_batch.hpp), and every method here
     is the C-ABI call of that name under the class's prefix.  A subclass sets members and precision, calls _create, and adds
     upload and download, which differ in how the members' arrays are laid out."""
@@ -374,31 +384,14 @@ class _Batch:
 
     def _create(self, opts, *args):
         """<prefix>_create(&handle, *args, &nbx_opts) on a library that has this kind's entry points."""
-        self._L = load()
+        self._new_handle()
+        self._destroy = self._prefix + "_destroy"
         where = self._prefix + "_create"
         if not hasattr(self._L, where):
             raise NbxError(NBX_ERR_STATE, where, "%s was built without %s" % (LIB_PATH, self._what))
-        self._h = ctypes.c_void_p()
         o = _opts(opts)
         _check(getattr(self._L, where)(ctypes.byref(self._h), *args, ctypes.byref(o)), where)
         self.dtype = _dtype(self.precision)
-
-    def close(self):
-        if self._h:
-            getattr(self._L, self._prefix + "_destroy")(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def step(self, nsteps, dt=DT, kenergy=True):
         """nsteps steps of every member; the kinetic energy of each member after the last one (array of `members`) if asked for."""
@@ -512,21 +505,18 @@ class Ragged(_Batch):
         return super().diagnostics(first, count)
 
 
-class Group:
+class Group(_Handle):
     """One nbx_group: n_ranks contexts driven by this process (multi-GPU; logical ranks when devices repeat)."""
+    _destroy = "nbx_group_destroy"
 
     def __init__(self, n, precision=32, n_ranks=1, devices=None, rank=None, unique_id=None, device=-1, weights=None, weighted=False, **opts):
         """Single process: n_ranks contexts on `devices`.  One process per GPU: pass rank= and unique_id= (the 128 bytes
         of unique_id() made on rank 0 and shipped to every rank); n_ranks is then the world size and every call on the
         group is collective (nbx_group_create_rank).  weights= (or weighted=True for equal weights): unequal shares in whole
         256-record tiles (nbx_group_create_weighted), which retune() can move."""
-        self._L = load()
-        self._h = ctypes.c_void_p()
+        self._new_handle()
         self.n, self.precision, self.dtype = int(n), int(precision), _dtype(precision)
-        o = Opts()
-        o.struct_size = ctypes.sizeof(Opts)
-        for k, v in opts.items():
-            setattr(o, k, v)
+        o = _opts(opts)  # the library sets the device of every rank itself
         if rank is not None:
             buf = ctypes.create_string_buffer(bytes(unique_id), UNIQUE_ID_BYTES)
             _check(self._L.nbx_group_create_rank(ctypes.byref(self._h), self.n, self.precision, n_ranks, rank, buf, device, ctypes.byref(o)),
@@ -541,16 +531,8 @@ class Group:
         _check(self._L.nbx_group_create(ctypes.byref(self._h), self.n, self.precision, n_ranks, dev, ctypes.byref(o)),
                "nbx_group_create")
 
-    def close(self):
-        if self._h:
-            self._L.nbx_group_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+    def __del__(self):  # never with the Python object: the destroy of a rank group is collective, and only close() starts one
+        pass
 
     def upload(self, state):
         arrs = [np.ascontiguousarray(state[f], dtype=self.dtype) for f in FIELDS]
