@@ -79,6 +79,9 @@ int nbx_ragged_upload(nbx_ragged* r, int32_t first, int32_t count, const void* p
  * the last step, the call synchronises and stores 0.5 * sum m v^2 of member m after the last step in kenergy_out[m].  With
  * nsteps == 0 it reports the energies the last step left (zeros if no step has run), as nbx_step does.
  * NBX_ERR_STATE until every member has been uploaded.
+ * dt is the time step of every member and of all nsteps steps, as nbx_step takes it: any finite value, zero and negative values
+ * included, converted to the ragged ensemble's precision by round-to-nearest.  NBX_ERR_ARG ("dt is not finite") for a NaN or an
+ * infinity, here and in nbx_ragged_step_trace, before the members' uploads are looked at.
  */
 int nbx_ragged_step(nbx_ragged* r, double dt, int32_t nsteps, double* kenergy_out /* [members] or NULL */);
 

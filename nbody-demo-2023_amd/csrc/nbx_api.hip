@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -331,6 +332,7 @@ static int step_common(nbx_ctx* c, double dt, int32_t nsteps, double* ke_last, d
   return guarded("nbx_step", [&]() -> int {
   if (!c) return fail(NBX_ERR_ARG, "nbx_step: ctx is NULL");
   if (nsteps < 0) return fail(NBX_ERR_ARG, "nbx_step: nsteps < 0");
+  if (!std::isfinite(dt)) return fail(NBX_ERR_ARG, "nbx_step: dt is not finite");  // a NaN equals no cached graph's dt, itself included
   if (!c->uploaded) return fail(NBX_ERR_STATE, "nbx_step: nbx_upload has not been called");
   if (c->i_begin != 0 || c->i_count != c->n)
     return fail(NBX_ERR_STATE, "nbx_step: context owns a slice; use nbx_step_local + exchange + nbx_commit");
@@ -390,6 +392,7 @@ int nbx_step_trace(nbx_ctx* c, double dt, int32_t nsteps, double* ke_trace) {
 int nbx_step_local(nbx_ctx* c, double dt) {
   return guarded("nbx_step_local", [&]() -> int {
   if (!c) return fail(NBX_ERR_ARG, "nbx_step_local: ctx is NULL");
+  if (!std::isfinite(dt)) return fail(NBX_ERR_ARG, "nbx_step_local: dt is not finite");
   if (!c->uploaded) return fail(NBX_ERR_STATE, "nbx_step_local: nbx_upload has not been called");
   if (c->pending_commit) return fail(NBX_ERR_STATE, "nbx_step_local: previous step not committed");
   int rc = use_device(c);

@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <utility>
@@ -124,6 +125,7 @@ int step_common(O* o, const char* where, double dt, int32_t nsteps, double* ke_l
   return guarded(where, [&]() -> int {
   if (!o) return fail(NBX_ERR_ARG, std::string(where) + ": " + O::names.noun + " is NULL");
   if (nsteps < 0) return fail(NBX_ERR_ARG, std::string(where) + ": nsteps < 0");
+  if (!std::isfinite(dt)) return fail(NBX_ERR_ARG, std::string(where) + ": dt is not finite");
   if (o->uploaded_count != o->members)
     return fail(NBX_ERR_STATE, std::string(where) + ": " + std::to_string(o->members - o->uploaded_count) + " of " + std::to_string(o->members) +
                                    " members have not been uploaded (" + O::names.prefix + "_upload)");

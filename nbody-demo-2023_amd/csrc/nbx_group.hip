@@ -636,6 +636,7 @@ int nbx_group_step(nbx_group* g, double dt, int32_t nsteps, double* kenergy_out)
   return guarded("nbx_group_step", [&]() -> int {
   if (!g) return fail(NBX_ERR_ARG, "nbx_group_step: group is NULL");
   if (nsteps < 0) return fail(NBX_ERR_ARG, "nbx_group_step: nsteps < 0");
+  if (!std::isfinite(dt)) return fail(NBX_ERR_ARG, "nbx_group_step: dt is not finite");
   if (g->broken) return fail(NBX_ERR_STATE, "nbx_group_step: a retune failed while rebuilding the contexts; destroy the group");
   const auto t_enter = std::chrono::steady_clock::now();
   const bool window_from_sync = g->steps_unsynced == 0;  // everything this call waits for was enqueued by this call

@@ -1,5 +1,6 @@
 """High-precision direct sum of the softened-gravity acceleration, a per-body error metric, and the state families of the
-step probe (tests/test_step_probe_cpu.py, tests/test_step_probe_gpu.py).
+step probe (tests/test_step_probe_cpu.py, tests/test_step_probe_gpu.py) and of the moving probe (tests/test_moving_probe_cpu.py,
+tests/test_moving_probe_gpu.py), whose velocities and identities are at the end of the metric section.
 
 The values are taken as libnbx stores them: positions in T (fp32 or fp64), G*m rounded as nbx_upload rounds it
 (energy_ref.gm_as_uploaded), eps^2 = 1e-3f widened.  Every term
@@ -176,18 +177,54 @@ def k_metric(got, tr, precision):
     return K
 
 
-def accel_from_v1(vel, precision):
-    """The acceleration a step kernel applied, from the velocities one step after an upload with v = 0: euler_update rounds
-    v1 = fl(a dt), so v1 / dt is a to half an ulp of T.  vel: (rows, 3) in T."""
+def accel_from_v1(vel, precision, dt=DT):
+    """The acceleration a step kernel applied, from the velocities one step of `dt` after an upload with v = 0: euler_update
+    rounds v1 = fl(a dt), so v1 / dt is a to half an ulp of T.  vel: (rows, 3) in T; dt: a value of T (exact in the wide type)."""
     wide = np.longdouble if (precision == 64 and HAVE_LONGDOUBLE) else np.float64
-    return np.asarray(vel).astype(wide) / wide(DT)
+    return np.asarray(vel).astype(wide) / wide(dt)
 
 
-def position_identity(p0, v1, precision):
-    """fl(p0 + fl(v1 dt)) in T, as euler_update evaluates it: must equal the downloaded position bit for bit."""
+def position_identity(p0, v1, precision, dt=DT):
+    """fl(p0 + fl(v1 dt)) in T, as euler_update evaluates it: must equal the downloaded position bit for bit.  dt is converted
+    to T by round-to-nearest, as the library converts the double it is given."""
     T = np.float32 if precision == 32 else np.float64
     p0, v1 = np.asarray(p0, dtype=T), np.asarray(v1, dtype=T)
-    return (p0 + (v1 * T(DT)).astype(T)).astype(T)
+    return (p0 + (v1 * T(dt)).astype(T)).astype(T)
+
+
+def velocity_identity(v0, v1_rest, precision):
+    """fl(v0 + v1_rest) in T.  v1_rest = fl(a dt) is what one step leaves from rest; the acceleration depends on the positions
+    only, so the same step from v0 must leave exactly this (euler_update: v = add_rn(v, mul_rn(a, dt)))."""
+    T = np.float32 if precision == 32 else np.float64
+    return (np.asarray(v0, dtype=T) + np.asarray(v1_rest, dtype=T)).astype(T)
+
+
+def moving_identity_failures(p0, v0, v1_rest, v1, p1, precision, dt):
+    """(rows where v1 != fl(v0 + v1_rest), rows where p1 != fl(p0 + fl(v1 dt))) of one moving step; all arrays (rows, 3) in T."""
+    bad_v = np.flatnonzero((np.asarray(v1) != velocity_identity(v0, v1_rest, precision)).any(axis=1))
+    bad_p = np.flatnonzero((np.asarray(p1) != position_identity(p0, v1, precision, dt)).any(axis=1))
+    return bad_v, bad_p
+
+
+MOVING_RECIPES =("uniform in [-1, 1]", "fl(v1_rest u), u uniform in [-4, 4]", "-v1_rest", "0", "fl(v1_rest 1e3 N(0, 1))")
+
+
+def moving_velocities(v1_rest, precision, seed):
+    """(n, 3) initial velocities in T for the moving probe; body i takes MOVING_RECIPES[i % 5]: far above a dt; of the magnitude
+    of a dt, where the rounding of the add matters; cancelling to zero exactly; zero; and a thousand times a dt with either
+    sign.  Every body and component draws its own number, so an index or component mix-up cannot cancel."""
+    T = np.float32 if precision == 32 else np.float64
+    r = np.asarray(v1_rest, dtype=T)
+    n = r.shape[0]
+    rng = np.random.default_rng([seed, n, precision])
+    draws = (rng.uniform(-1.0, 1.0, (n, 3)), rng.uniform(-4.0, 4.0, (n, 3)), rng.standard_normal((n, 3)))
+    k = (np.arange(n) % 5)[:, None]
+    v = np.zeros((n, 3), dtype=T)
+    v = np.where(k == 0, draws[0].astype(T), v)
+    v = np.where(k == 1, (r * draws[1].astype(T)).astype(T), v)
+    v = np.where(k == 2, -r, v)
+    v = np.where(k == 4, ((r * T(1e3)).astype(T) * draws[2].astype(T)).astype(T), v)
+    return v.astype(T)
 
 
 # ---- the reference's own arithmetic --------------------------------------------------------------------------------------------

@@ -150,3 +150,42 @@ def test_create_on_a_device_that_is_not_there(nbx, prefix, noun):
     rc, text = _raw_create(nbx, prefix, ctypes.byref(h), ctypes.byref(o))
     assert rc == nbx.NBX_ERR_ARG and text == prefix + "_create: device ordinal out of range", text
     assert not h.value
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# a time step that is not finite: after the NULL-handle and nsteps checks, before the members' uploads are looked at
+# ---------------------------------------------------------------------------------------------------------------------------
+NOT_FINITE = (float("nan"), float("inf"), float("-inf"))
+
+
+@pytest.mark.parametrize("prefix,noun", KINDS)
+def test_a_null_handle_is_reported_before_a_time_step_that_is_not_finite(nbx, prefix, noun):
+    d = (ctypes.c_double * 4)()
+    for dt in NOT_FINITE:
+        for fn in ("_step", "_step_trace"):
+            rc, text = _call(nbx, prefix + fn, ctypes.c_void_p(), dt, 1, d)
+            assert rc == nbx.NBX_ERR_ARG and text == "%s%s: %s is NULL" % (prefix, fn, noun), (fn, dt, text)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prefix,noun", KINDS)
+def test_a_time_step_that_is_not_finite_is_refused(nbx, prefix, noun):
+    sizes = SIZES[prefix]
+    ke = (ctypes.c_double * 8)()
+    states = [nbx.initial_conditions(n, 32) for n in sizes]
+    with _make(nbx, prefix) as o:
+        for uploaded in (False, True):
+            for dt in NOT_FINITE:
+                for fn, args in (("_step", (o._h, dt, 1, ke)), ("_step", (o._h, dt, 0, None)), ("_step_trace", (o._h, dt, 2, ke))):
+                    rc, text = _call(nbx, prefix + fn, *args)
+                    assert rc == nbx.NBX_ERR_ARG and text == "%s%s: dt is not finite" % (prefix, fn), (fn, dt, uploaded, rc, text)
+                for fn in ("_step", "_step_trace"):  # nsteps is looked at first
+                    rc, text = _call(nbx, prefix + fn, o._h, dt, -1, ke)
+                    assert rc == nbx.NBX_ERR_ARG and text == "%s%s: nsteps < 0" % (prefix, fn), (fn, text)
+            if not uploaded:
+                o.upload(states)
+        assert o.stats()["steps_done"] == 0
+        d = o.download()
+        for m, s0 in enumerate(states):
+            for f in nbx.FIELDS[:6]:
+                assert (d[f][m] == s0[f]).all() if prefix == "nbx_ensemble" else (d[m][f] == s0[f]).all(), (m, f)

@@ -3,7 +3,7 @@ nbx_last_error() gives for each, with its return code, through raw C-ABI calls. 
 caller sees, and the host layer under the context may be reorganised only if every one of them comes out byte for byte.
 
 The first part needs no GPU (every case returns before the first HIP call); the second creates the smallest contexts, 65
-bodies in fp32, and launches one step at most."""
+bodies in fp32, and launches a few steps at most."""
 import ctypes
 
 import pytest
@@ -191,3 +191,73 @@ def test_nbx_step_on_a_context_that_owns_a_slice(nbx):
             assert rc == nbx.NBX_ERR_STATE, (fn, rc)
             assert text == "nbx_step: context owns a slice; use nbx_step_local + exchange + nbx_commit", (fn, text)
         assert c.stats()["steps_done"] == 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# a time step that is not finite: after the NULL-handle and nsteps checks, before the state is looked at
+# ---------------------------------------------------------------------------------------------------------------------------
+NOT_FINITE = (float("nan"), float("inf"), float("-inf"))
+
+
+def test_a_null_handle_and_nsteps_are_reported_before_a_time_step_that_is_not_finite(nbx):
+    null = ctypes.c_void_p()
+    ke = (ctypes.c_double * 4)()
+    for dt in NOT_FINITE:
+        for fn, args, want in (("nbx_step", (null, dt, 1, ke), "nbx_step: ctx is NULL"), ("nbx_step_trace", (null, dt, 1, ke), "nbx_step: ctx is NULL"),
+                               ("nbx_step_local", (null, dt), "nbx_step_local: ctx is NULL"),
+                               ("nbx_group_step", (null, dt, 1, ke), "nbx_group_step: group is NULL"),
+                               ("nbx_group_step", (null, dt, -1, ke), "nbx_group_step: group is NULL")):
+            rc, text = _call(nbx, fn, *args)
+            assert rc == nbx.NBX_ERR_ARG and text == want, (fn, dt, rc, text)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("use_graph", [1, 2])
+def test_a_time_step_that_is_not_finite_is_refused(nbx, use_graph):
+    """NaN and both infinities, before and after an upload.  A NaN equals no cached graph's dt, its own included: with graph
+    replay on, every such call used to capture and keep one more graph until nbx_destroy."""
+    ke = (ctypes.c_double * 8)()
+    s0 = nbx.initial_conditions(N, 32)
+    with nbx.Context(N, 32, use_graph=use_graph) as c:
+        h = c._h
+        for uploaded in (False, True):
+            for dt in NOT_FINITE:
+                for fn, args, want in (("nbx_step", (h, dt, 8, ke), "nbx_step"), ("nbx_step", (h, dt, 0, None), "nbx_step"),
+                                       ("nbx_step_trace", (h, dt, 8, ke), "nbx_step"), ("nbx_step_local", (h, dt), "nbx_step_local")):
+                    rc, text = _call(nbx, fn, *args)
+                    assert rc == nbx.NBX_ERR_ARG and text == want + ": dt is not finite", (fn, dt, uploaded, rc, text)
+                for fn in ("nbx_step", "nbx_step_trace"):  # nsteps is looked at first
+                    rc, text = _call(nbx, fn, h, dt, -1, ke)
+                    assert rc == nbx.NBX_ERR_ARG and text == "nbx_step: nsteps < 0", (fn, text)
+            if not uploaded:
+                rc, text = _call(nbx, "nbx_step", h, 0.1, 1, ke)  # a finite one gets as far as the state
+                assert rc == nbx.NBX_ERR_STATE and text == "nbx_step: nbx_upload has not been called", text
+                c.upload(s0)
+        st = c.stats()
+        assert st["steps_done"] == 0 and st["graph_replays"] == 0, st
+        rc, text = _call(nbx, "nbx_commit", h)  # a refused local step leaves nothing to commit
+        assert rc == nbx.NBX_ERR_STATE and text == "nbx_commit: no local step pending", text
+        d = c.download()
+        for f in d:
+            assert (d[f] == s0[f]).all(), f
+        # zero and negative time steps are time steps
+        ke0 = c.step(8, dt=0.0)
+        assert ke0 > 0 and c.step(8, dt=-0.0) == ke0 and c.step(2, dt=-0.125) > 0 and c.stats()["steps_done"] == 18
+
+
+@pytest.mark.gpu
+def test_a_group_refuses_a_time_step_that_is_not_finite(nbx):
+    ke = ctypes.c_double()
+    s0 = nbx.initial_conditions(N, 32)
+    with nbx.Group(N, 32, n_ranks=1, devices=[0]) as g:
+        for uploaded in (False, True):
+            for dt in NOT_FINITE:
+                rc, text = _call(nbx, "nbx_group_step", g._h, dt, 1, ctypes.byref(ke))
+                assert rc == nbx.NBX_ERR_ARG and text == "nbx_group_step: dt is not finite", (dt, uploaded, rc, text)
+                rc, text = _call(nbx, "nbx_group_step", g._h, dt, -1, ctypes.byref(ke))
+                assert rc == nbx.NBX_ERR_ARG and text == "nbx_group_step: nsteps < 0", (dt, text)
+            g.upload(s0)
+        assert g.info(0)[2]["steps_done"] == 0
+        d = g.download()
+        for f in d:
+            assert (d[f] == s0[f]).all(), f
