@@ -11,7 +11,7 @@ lib: $(PKG)/libnbx.so
 
 $(PKG)/nbx_api.o: $(CSRC)/nbx_api.hip $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_kernels.hpp $(CSRC)/nbx_jlane.hpp $(CSRC)/nbx_pair.hpp $(CSRC)/nbx_sgpr_loop.inc $(CSRC)/nbx_jlane_loop.inc include/nbx.h include/nbx_diag.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_group.o: $(CSRC)/nbx_group.hip $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_watchdog.hpp include/nbx.h include/nbx_diag.h
+$(PKG)/nbx_group.o: $(CSRC)/nbx_group.hip $(CSRC)/nbx_shares.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_watchdog.hpp include/nbx.h include/nbx_diag.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(PKG)/nbx_diag.o: $(CSRC)/nbx_diag.hip $(CSRC)/nbx_diag_kernels.hpp $(CSRC)/nbx_diag_body.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@

@@ -1525,6 +1525,22 @@ def test_the_tuner_predicts_before_it_moves_and_takes_back_what_made_the_step_sl
         assert g.shares(timings=False)[1] == after
 
 
+def test_recorded_retune_scenarios_on_the_device(nbx):
+    """tests/golden/group_shares.json, `retune`: what nbx_group_retune decided before the share planner moved to csrc/nbx_shares.hpp
+    (tools/record_group_shares.py; one scenario per branch of the decision).  Logical ranks on device 0, the recorded force_ms, nothing
+    stepped: the same `changed` flag and the same shares after every call.  tests/test_shares_cpu.py replays them without a device."""
+    d = load_golden("group_shares.json")
+    assert len(d["retune"]) >= 10
+    for s in d["retune"]:
+        with nbx.Group(s["n"], s["precision"], n_ranks=s["ranks"], devices=[0] * s["ranks"], weights=s["weights"], weighted=True, **s["opts"]) as g:
+            g.upload(nbx.initial_conditions(s["n"], s["precision"]))
+            assert g.info(0)[2]["cu_count"] == d["cu_count"]
+            assert g.shares(timings=False)[:2] == (s["begin"], s["count"]), s["name"]
+            for c in s["calls"]:
+                changed = g.retune(c["force_ms"])
+                assert (int(changed),) + g.shares(timings=False)[:2] == (c["changed"], c["begin"], c["count"]), (s["name"], c)
+
+
 @pytest.mark.parametrize("prec,tol", [(32, 2e-6), (64, 1e-12)])
 def test_weighted_shares_in_tree_order_and_fp64_stay_inside_the_rounding_band(nbx, prec, tol):
     """Tree order: the summation tree of a body depends on the launch shape of whoever owns it, so shares and retunes move results
