@@ -23,7 +23,7 @@
  * the kinetic energy is asked for); no graph capture.
  *
  * Deliberately not here: a time step per member; the diagnostics of nbx_diag.h for ragged members; sharding over GPUs (run
- * one ragged ensemble per GPU); nbx_accel; the reference summation order and the exact (validation) kernel; hipGraph replay;
+ * one ragged ensemble per GPU); nbx_accel (nbx_batch_accel.h has it); the reference summation order and the exact (validation) kernel; hipGraph replay;
  * a command-line word in nbody.x (its argv is the reference's).
  */
 #ifndef NBX_RAGGED_H

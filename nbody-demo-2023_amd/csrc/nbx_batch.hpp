@@ -1,8 +1,8 @@
 // nbx_batch.hpp -- the host side that ensembles (nbx_ensemble.hip, nbx_ensemble_diag.hip) and ragged ensembles (nbx_ragged.hip,
 // nbx_ragged_diag.hip) share on top of what every device object has (nbx_object.hpp: the fields, device choice, the energy
 // trace, profiling, create / destroy -- the context, nbx_internal.hpp, stands on that base too): the member bookkeeping and
-// checks, the step loop, the launcher table, upload and download over a member-layout lookup, stats, and the diagnostics entry
-// point.  Host-only: it defines no kernel and includes no kernel header, so every translation unit keeps compiling exactly the
+// checks, the step loop, the launcher tables, upload and download over a member-layout lookup, stats, and the diagnostics and
+// accelerations entry points.  Host-only: it defines no kernel and includes no kernel header, so every translation unit keeps compiling exactly the
 // kernels it includes itself.
 //
 // A kind is a struct derived from Batch (nbx_ensemble, nbx_ragged) that adds
@@ -43,6 +43,7 @@ struct Batch : Object {
   std::vector<char> uploaded;  // per member
   int uploaded_count = 0;
   // ke_dev: slot s of member m at s * members + m; diag_part is [rows][9], diag_dev [members][9]
+  void* accm = nullptr;  // *_accel (nbx_batch_accel.hip): {ax, ay, az, 0} records laid out as velm, allocated on first use; the kind's destroy frees it
 };
 
 // *_stats up to the fields of the kind: the checks, the pending events drained, *s cleared and the fields every kind reports
@@ -328,6 +329,60 @@ int batch_diagnostics(O* o, const char* where, int32_t first, int32_t count, nbx
   HIP_TRY(hipStreamSynchronize(o->stream));
   for (int k = 0; k < count; ++k) diag_fill(raw.data() + (size_t)k * Fields, o->layout(first + k).n, o->steps_done, out + k);
   return NBX_OK;
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// *_accel (include/nbx_batch_accel.h): the accelerations of members [first, first + count) at posm[cur] -- one launch over the
+// workgroups of those members, one copy of the range's span of the slab, one synchronisation.  The launcher table is the step's
+// over again: one launcher per entry of kEnsembleInstances, Launch::run<I>(o, first, count) launches the kind's accel kernel
+// for entry I.  `prepare(o)` is the kind's part of the first use (a ragged ensemble's work list).  The launch is not a step: it
+// is not timed, and have_parts, steps_done and cur do not see it.
+// ---------------------------------------------------------------------------------------------------------------------------
+template <typename O, typename Launch, int I>
+void launch_accel_instance(O* o, int first, int count) {
+  static_assert(nbx::kEnsembleInstances[I].kind == nbx::INST_JLANE, "a member's accelerations come from the one-launch kernel body");
+  Launch::template run<I>(o, first, count);
+}
+template <typename O, typename Launch, int... I>
+constexpr std::array<void (*)(O*, int, int), sizeof...(I)> make_accel_launchers(std::integer_sequence<int, I...>) {
+  return {{&launch_accel_instance<O, Launch, I>...}};
+}
+template <typename O, typename Launch>
+constexpr auto kAccelLaunchers = make_accel_launchers<O, Launch>(std::make_integer_sequence<int, nbx::kEnsembleInstanceCount>{});
+
+// first use: the slab, member k's n_alloc_k records at its vel_off -- the size and layout of velm, fixed for the object's life.
+// Not cleared: the kernel writes the records [0, n_k) of every member it is launched for, and download_records reads no other.
+template <typename O>
+int ensure_accel_slab(O* o, const char* where) {
+  if (o->accm) return NBX_OK;
+  char* dev = nullptr;
+  const int rc = device_alloc(&dev, o->rec * span_of(o, 0, o->members).vel_count, where, "the accelerations");
+  if (rc == NBX_OK) o->accm = dev;
+  return rc;
+}
+
+template <typename O, typename Launch, typename Prepare>
+int batch_accel(O* o, const char* where, int32_t first, int32_t count, void* ax, void* ay, void* az, Prepare prepare) {
+  return guarded(where, [&]() -> int {
+  if (!o) return fail(NBX_ERR_ARG, std::string(where) + ": " + O::names.noun + " is NULL");
+  int rc = check_range(o, where, first, count);
+  if (rc) return rc;
+  rc = check_uploaded(o, where, first, count);
+  if (rc) return rc;
+  if (count == 0 || (!ax && !ay && !az)) return NBX_OK;
+  const int k = nbx::ensemble_instance_index(o->plan.step);  // *_create has resolved the step's launcher from the same index
+  if (k < 0) return fail(NBX_ERR_STATE, std::string(where) + ": no kernel instance for this bodies_per_lane / precision");
+  rc = use_device(o);
+  if (rc) return rc;
+  rc = ensure_accel_slab(o, where);
+  if (rc) return rc;
+  rc = prepare(o);
+  if (rc) return rc;
+  kAccelLaunchers<O, Launch>[(size_t)k](o, first, count);
+  HIP_TRY(hipGetLastError());
+  return o->precision == 32 ? download_records<float>(o, first, count, o->accm, false, (float*)ax, (float*)ay, (float*)az)
+                            : download_records<double>(o, first, count, o->accm, false, (double*)ax, (double*)ay, (double*)az);
   });
 }
 

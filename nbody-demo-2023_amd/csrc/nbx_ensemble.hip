@@ -97,7 +97,8 @@ int nbx_ensemble_create(nbx_ensemble** out, int32_t n, int32_t precision, int32_
 void nbx_ensemble_destroy(nbx_ensemble* e) {
   if (!e) return;
   batch_quiesce(e);
-  batch_release(e);  // every device buffer of an ensemble is one both kinds have
+  if (e->accm) (void)hipFree(e->accm);  // the slab of nbx_batch_accel.hip
+  batch_release(e);                     // every other device buffer of an ensemble is one every object has
   delete e;
 }
 

@@ -604,6 +604,32 @@ inline int plan_ragged(const int* n, int members, int precision, int cus, const 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// Accelerations of the members of a ragged ensemble (include/nbx_batch_accel.h): one launch over a 1-D grid whose workgroup
+// blockIdx.x reads one RaggedWork descriptor, as the step does, from a list in MEMBER order, where the step's is longest-first.
+// With member order the workgroups of members [first, first + count) are the contiguous slice work_begin[first] ..
+// work_begin[first + count) of the list, so no call builds or uploads a list.  The descriptors are plan_ragged's own -- the
+// member's offsets from its member table, wg = 0 .. grid_k - 1 in order -- so a member runs the workgroups its step runs.
+// Nobody has measured whether longest-first within a range would be faster; a range is usually a few members.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct RaggedAccelPlan {
+  std::vector<unsigned> work_begin;  // [members + 1]: prefix sum of the members' workgroups (RaggedMember::grid)
+  std::vector<RaggedWork> work;      // [W], member order; within a member by wg
+};
+
+inline void plan_ragged_accel(const RaggedPlan& rp, RaggedAccelPlan* a) {
+  *a = RaggedAccelPlan{};
+  const size_t members = rp.member.size();
+  a->work_begin.assign(members + 1, 0u);
+  a->work.reserve((size_t)rp.W);
+  for (size_t k = 0; k < members; ++k) {
+    const RaggedMember& m = rp.member[k];
+    a->work_begin[k] = (unsigned)a->work.size();
+    for (int wg = 0; wg < m.grid; ++wg) a->work.push_back({m.pos_off, m.vel_off, m.ke_off, (unsigned)wg, m.n, m.n_alloc, (unsigned)k, 0u});
+  }
+  a->work_begin[members] = (unsigned)a->work.size();  // = rp.W
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // Diagnostics of the members of a ragged ensemble (include/nbx_ragged_diag.h): one pair-work launch over a 1-D grid whose
 // workgroup blockIdx.x reads one RaggedDiagWork descriptor and runs diag_body (nbx_diag_body.hpp) on it, one reduce launch over
 // the members asked for.  Member k's shape is exactly what enqueue_diag_t (nbx_diag.hip) gives a context of n_k bodies that owns

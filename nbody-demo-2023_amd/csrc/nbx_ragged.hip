@@ -108,6 +108,8 @@ void nbx_ragged_destroy(nbx_ragged* r) {
   if (r->parts_dev) (void)hipFree(r->parts_dev);
   if (r->diag_work_dev) (void)hipFree(r->diag_work_dev);  // the tables of nbx_ragged_diag.hip
   if (r->diag_rows_dev) (void)hipFree(r->diag_rows_dev);
+  if (r->accel_work_dev) (void)hipFree(r->accel_work_dev);  // the table and the slab of nbx_batch_accel.hip
+  if (r->accm) (void)hipFree(r->accm);
   batch_release(r);
   delete r;
 }

@@ -1,10 +1,10 @@
 // nbx_ragged_internal.hpp -- the ragged-ensemble object, shared by the translation units that serve it: nbx_ragged.hip (create,
-// upload, step, download) and nbx_ragged_diag.hip (diagnostics).  Not part of the C-ABI (include/nbx_ragged.h is).  It names no
-// kernel header, so that each of the two units compiles exactly the kernels it includes itself.  What a ragged ensemble has in
+// upload, step, download), nbx_ragged_diag.hip (diagnostics) and nbx_batch_accel.hip (accelerations).  Not part of the C-ABI (include/nbx_ragged.h is).  It names no
+// kernel header, so that each of these units compiles exactly the kernels it includes itself.  What a ragged ensemble has in
 // common with an ensemble -- most of its fields and all of its host plumbing -- is nbx_batch.hpp.
 #pragma once
 #include "../../include/nbx_ragged.h"
-#include "nbx_batch.hpp"  // nbx_detail::Batch; error plumbing; nbx_plan.hpp: nbx::RaggedPlan, nbx::RaggedDiagPlan
+#include "nbx_batch.hpp"  // nbx_detail::Batch; error plumbing; nbx_plan.hpp: nbx::RaggedPlan, nbx::RaggedDiagPlan, nbx::RaggedAccelPlan
 
 namespace nbx {
 struct RaggedParts;  // nbx_ragged_kernels.hpp: the table ragged_ke_reduce_kernel reads
@@ -24,6 +24,10 @@ struct nbx_ragged : nbx_detail::Batch {
   bool have_diag_plan = false;
   nbx::RaggedDiagWork* diag_work_dev = nullptr;
   nbx::RaggedDiagRows* diag_rows_dev = nullptr;
+  // accelerations (nbx_batch_accel.hip), built and uploaded on first use likewise: the member-order work list of plan_ragged_accel
+  nbx::RaggedAccelPlan accel_plan;
+  bool have_accel_plan = false;
+  nbx::RaggedWork* accel_work_dev = nullptr;  // [plan.W]
   nbx_detail::MemberSpan layout(int k) const {
     const nbx::RaggedMember& m = plan.member[(size_t)k];
     return {m.pos_off, m.vel_off, m.n, m.n_alloc};

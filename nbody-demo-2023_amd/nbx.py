@@ -49,6 +49,9 @@ RAGGED_SYMBOLS = (
 # the symbol of include/nbx_ragged_diag.h (the diagnostics of every member of a ragged ensemble in one launch), kept apart likewise
 RAGGED_DIAG_SYMBOLS = ("nbx_ragged_diagnostics",)
 
+# the symbols of include/nbx_batch_accel.h (the accelerations of the members of either kind in one launch), kept apart likewise
+BATCH_ACCEL_SYMBOLS = ("nbx_ensemble_accel", "nbx_ragged_accel")
+
 
 class NbxError(RuntimeError):
     def __init__(self, code, where, text):
@@ -214,6 +217,9 @@ def load():
         L.nbx_ragged_stats.argtypes = [vp, ctypes.POINTER(RaggedStats)]
     if hasattr(L, "nbx_ragged_diagnostics"):  # likewise for nbx_ragged_diag.hip
         L.nbx_ragged_diagnostics.argtypes = [vp, i32, i32, ctypes.POINTER(Diag)]
+    if hasattr(L, "nbx_ensemble_accel"):  # likewise for nbx_batch_accel.hip
+        L.nbx_ensemble_accel.argtypes = [vp, i32, i32, vp, vp, vp]
+        L.nbx_ragged_accel.argtypes = [vp, i32, i32, vp, vp, vp]
     _lib = L
     return L
 
@@ -429,6 +435,13 @@ class _Batch(_Handle):
         self._call("diagnostics", first, count, d)
         return [d[k].asdict() for k in range(max(count, 0))]
 
+    def _accel(self, first, count, arrs):
+        """<prefix>_accel into three host arrays (None skips one).  Synchronises."""
+        where = self._prefix + "_accel"
+        if not hasattr(self._L, where):
+            raise NbxError(NBX_ERR_STATE, where, "%s was built without %s" % (LIB_PATH, where))
+        self._call("accel", first, count, *[_ptr(a) for a in arrs])
+
 
 class Ensemble(_Batch):
     """One nbx_ensemble (include/nbx_ensemble.h): `members` independent systems of n bodies, one launch per time step for all
@@ -455,6 +468,15 @@ class Ensemble(_Batch):
         out = {f: np.zeros((max(count, 0), self.n), dtype=self.dtype) for f in FIELDS[:6]}
         self._call("download", first, count, *[_ptr(out[f]) for f in FIELDS[:6]])
         return out
+
+    def accel(self, first=0, count=None):
+        """nbx_ensemble_accel: [ax, ay, az], each (count, n), of members [first, first + count) (default: all from `first`) at the
+        current positions -- for each member the bits Context.accel() returns for a jlane context of n bodies holding its state;
+        one launch for all of them.  Synchronises."""
+        count = self.members - first if count is None else count
+        a = [np.zeros((max(count, 0), self.n), dtype=self.dtype) for _ in range(3)]
+        self._accel(first, count, a)
+        return a
 
     def diagnostics(self, first=0, count=None):
         """nbx_ensemble_diagnostics: one dict per member of [first, first + count) (default: all from `first`), each what
@@ -497,6 +519,17 @@ class Ragged(_Batch):
         self._call("download", first, count, *[_ptr(flat[f]) for f in FIELDS[:6]])
         at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
         return [{f: flat[f][at[k]:at[k + 1]].copy() for f in FIELDS[:6]} for k in range(len(sizes))]
+
+    def accel(self, first=0, count=None):
+        """nbx_ragged_accel: one [ax, ay, az] per member of [first, first + count) (default: all from `first`) at the current
+        positions -- the bits Context.accel() returns for a jlane context of sizes[k] bodies holding that member's state; one
+        launch for all of them.  Synchronises."""
+        count = self.members - first if count is None else count
+        sizes = self._range(first, count)
+        flat = [np.zeros(max(sum(sizes), 1), dtype=self.dtype) for _ in range(3)]  # >= 1: _ptr wants an address, also for an empty range
+        self._accel(first, count, flat)
+        at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+        return [[a[at[k]:at[k + 1]].copy() for a in flat] for k in range(len(sizes))]
 
     def diagnostics(self, first=0, count=None):
         """nbx_ragged_diagnostics: one dict per member of [first, first + count) (default: all from `first`), each what
