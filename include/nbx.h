@@ -162,7 +162,8 @@ int nbx_upload(nbx_ctx* ctx, const void* pos_x, const void* pos_y, const void* p
  *
  * dt, here and in every other entry point that takes one (nbx_step_trace, nbx_step_local, nbx_group_step), is the time step
  * of all nsteps steps: any finite value, zero and negative values included (dt == 0 leaves positions and velocities as they
- * are; dt < 0 steps backwards with the same first-order update, which does not retrace a forward step).  It is converted to the
+ * are; dt < 0 steps backwards with the same first-order update, which does not retrace a forward step -- nbx_kick.h has the half
+ * kicks that make it do so).  It is converted to the
  * context's precision by round-to-nearest -- an fp32 context given the double 0.1 steps with (float)0.1, the reference's
  * _tstep -- and both updates of a step use that one value.  A NaN or an infinity is refused with NBX_ERR_ARG ("dt is not
  * finite"), after the handle and nsteps have been looked at and before the state is.  With graph replay on, the context keeps

@@ -23,6 +23,7 @@
  * Deliberately not here: members of different n (nbx_ragged.h has them); sharding one ensemble over GPUs (run one ensemble per GPU); nbx_accel for
  * ensembles (nbx_batch_accel.h has it); the reference summation order and the exact (validation) kernel; hipGraph replay; a command-line word in nbody.x
  * (its argv is the reference's).  The diagnostics of nbx_diag.h for the members of an ensemble are in nbx_ensemble_diag.h.
+ * Velocity-only half steps, which make the steps of every member kick-drift-kick leapfrog, are in nbx_kick.h.
  */
 #ifndef NBX_ENSEMBLE_H
 #define NBX_ENSEMBLE_H

@@ -24,7 +24,8 @@
  *
  * Deliberately not here: a time step per member; the diagnostics of nbx_diag.h for ragged members; sharding over GPUs (run
  * one ragged ensemble per GPU); nbx_accel (nbx_batch_accel.h has it); the reference summation order and the exact (validation) kernel; hipGraph replay;
- * a command-line word in nbody.x (its argv is the reference's).
+ * a command-line word in nbody.x (its argv is the reference's).  Velocity-only half steps, which make the steps of every member
+ * kick-drift-kick leapfrog, are in nbx_kick.h.
  */
 #ifndef NBX_RAGGED_H
 #define NBX_RAGGED_H

@@ -77,15 +77,15 @@ constexpr std::array<void (*)(nbx_ctx*, double, int), sizeof...(I)> make_launche
 }
 constexpr auto kLaunchers = make_launchers(std::make_integer_sequence<int, kInstanceCount>{});
 
-// the step kernel, or (accel) nbx_accel's slab form of it
-int enqueue_force(nbx_ctx* c, bool accel, double dt) {
+// the step kernel, or (accel) nbx_accel's slab form of it; timed = false: a launch the profile of the force kernel does not see
+int enqueue_force(nbx_ctx* c, bool accel, double dt, bool timed = true) {
   if (c->plan.pairs) {  // this step's pair-interleaved copy of the records (all n_alloc of them: other ranks' blocks arrived by all-gather)
     const int npairs = c->n_alloc / 2;
     hipLaunchKernelGGL(pair_transpose_kernel, dim3(ceil_div(npairs, kBlock)), dim3(kBlock), 0, c->stream, (const float4*)c->posm[c->cur],
                        (float4*)c->posm_pairs, npairs);
   }
   // the force launch alone is timed, and the exact kernel (validation) is not
-  return timed_launch(c, c->plan.step.kind != INST_EXACT, [&] { (accel ? c->launch_accel : c->launch_step)(c, dt, accel ? 1 : 0); });
+  return timed_launch(c, timed && c->plan.step.kind != INST_EXACT, [&] { (accel ? c->launch_accel : c->launch_step)(c, dt, accel ? 1 : 0); });
 }
 
 // energy partials one step of this context's shape writes: one per workgroup of the kernel that integrates
@@ -149,6 +149,8 @@ int nbx_detail::enqueue_ke_reduce(nbx_ctx* c, int slot) {
   HIP_TRY(hipGetLastError());
   return NBX_OK;
 }
+// nbx_kick (nbx_kick.hip): the launch nbx_accel reads back -- the accelerations at posm[cur] into the S slabs of accp -- not timed
+int nbx_detail::enqueue_accel_slabs(nbx_ctx* c) { return enqueue_force(c, true, 0.0, false); }
 // the tuner's predictor: nbx_plan.hpp, force_cost
 double nbx_detail::model_force_cost(const nbx_ctx* c, int own) { return force_cost(c->plan, c->precision, c->prop.multiProcessorCount, own); }
 

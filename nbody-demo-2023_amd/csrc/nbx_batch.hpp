@@ -1,8 +1,8 @@
 // nbx_batch.hpp -- the host side that ensembles (nbx_ensemble.hip, nbx_ensemble_diag.hip) and ragged ensembles (nbx_ragged.hip,
 // nbx_ragged_diag.hip) share on top of what every device object has (nbx_object.hpp: the fields, device choice, the energy
 // trace, profiling, create / destroy -- the context, nbx_internal.hpp, stands on that base too): the member bookkeeping and
-// checks, the step loop, the launcher tables, upload and download over a member-layout lookup, stats, and the diagnostics and
-// accelerations entry points.  Host-only: it defines no kernel and includes no kernel header, so every translation unit keeps compiling exactly the
+// checks, the step loop, the launcher tables, upload and download over a member-layout lookup, stats, and the diagnostics,
+// accelerations and kick entry points.  Host-only: it defines no kernel and includes no kernel header, so every translation unit keeps compiling exactly the
 // kernels it includes itself.
 //
 // A kind is a struct derived from Batch (nbx_ensemble, nbx_ragged) that adds
@@ -172,6 +172,53 @@ constexpr std::array<void (*)(O*, double), sizeof...(I)> make_launchers(std::int
 }
 template <typename O, typename Launch>
 constexpr auto kLaunchers = make_launchers<O, Launch>(std::make_integer_sequence<int, nbx::kEnsembleInstanceCount>{});
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// *_kick (include/nbx_kick.h): v += a(x) * h for every body of every member -- ONE launch over the step's own grid through a
+// third launcher table, one launcher per entry of kEnsembleInstances: Launch::run<I>(o, h) launches the kind's kick kernel
+// (nbx_kick_kernels.hpp, instantiated by nbx_kick.hip alone) for entry I.  Beside step_common because it ends as a step does:
+// the launch leaves ke_part describing the kicked velocities (have_parts), and an energy asked for takes the step's reduce and
+// read-back.  It is not a step otherwise: cur, steps_done and the profile of the step kernel do not see it (the launch is not
+// timed).  Every check comes before the first HIP call.
+// ---------------------------------------------------------------------------------------------------------------------------
+template <typename O, typename Launch, int I>
+void launch_kick_instance(O* o, double h) {
+  static_assert(nbx::kEnsembleInstances[I].kind == nbx::INST_JLANE, "a member is kicked by the one-launch kernel body");
+  Launch::template run<I>(o, h);
+}
+template <typename O, typename Launch, int... I>
+constexpr std::array<void (*)(O*, double), sizeof...(I)> make_kick_launchers(std::integer_sequence<int, I...>) {
+  return {{&launch_kick_instance<O, Launch, I>...}};
+}
+template <typename O, typename Launch>
+constexpr auto kKickLaunchers = make_kick_launchers<O, Launch>(std::make_integer_sequence<int, nbx::kEnsembleInstanceCount>{});
+
+template <typename O, typename Launch>
+int kick_common(O* o, const char* where, double h, double* ke_out) {
+  return guarded(where, [&]() -> int {
+  if (!o) return fail(NBX_ERR_ARG, std::string(where) + ": " + O::names.noun + " is NULL");
+  if (!std::isfinite(h)) return fail(NBX_ERR_ARG, std::string(where) + ": h is not finite");
+  int rc = check_uploaded(o, where, 0, o->members);
+  if (rc) return rc;
+  const int k = nbx::ensemble_instance_index(o->plan.step);  // *_create has resolved the step's launcher from the same index
+  if (k < 0) return fail(NBX_ERR_STATE, std::string(where) + ": no kernel instance for this bodies_per_lane / precision");
+  rc = use_device(o);
+  if (rc) return rc;
+  const size_t S = (size_t)o->members;
+  if (ke_out) {
+    rc = ensure_ke_cap(o, where, S);
+    if (rc) return rc;
+  }
+  kKickLaunchers<O, Launch>[(size_t)k](o, h);
+  HIP_TRY(hipGetLastError());
+  o->have_parts = true;  // of the kicked velocities: what a following step call of no steps reports
+  if (ke_out) {
+    rc = enqueue_ke_reduce(o, 0);
+    if (rc) return rc;
+  }
+  return read_energies(o, S, 1, true, ke_out, nullptr, [] { return (int)NBX_OK; });  // without ke_out: no copy, no synchronisation
+  });
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // upload and download

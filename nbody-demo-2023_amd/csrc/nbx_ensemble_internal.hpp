@@ -1,5 +1,5 @@
 // nbx_ensemble_internal.hpp -- the ensemble object, shared by the translation units that serve it: nbx_ensemble.hip (create,
-// upload, step, download), nbx_ensemble_diag.hip (diagnostics) and nbx_batch_accel.hip (accelerations).  Not part of the C-ABI (include/nbx_ensemble.h is).  What an
+// upload, step, download), nbx_ensemble_diag.hip (diagnostics) nbx_batch_accel.hip (accelerations) and nbx_kick.hip (kicks).  Not part of the C-ABI (include/nbx_ensemble.h is).  What an
 // ensemble has in common with a ragged ensemble -- most of its fields and all of its host plumbing -- is nbx_batch.hpp.
 #pragma once
 #include "../../include/nbx_ensemble.h"

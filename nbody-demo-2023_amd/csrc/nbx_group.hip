@@ -17,6 +17,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "../../include/nbx_kick.h"  // nbx_kick, nbx_group_kick
 #include "nbx_internal.hpp"
 #include "nbx_shares.hpp"  // who owns what, and the tuner: all the arithmetic of this file
 #include "nbx_watchdog.hpp"
@@ -206,6 +207,31 @@ int gather_rows(nbx_group* g, const void* row, size_t bytes, void* all, void* ho
   if (e != ncclSuccess) return rccl_fail(what, e);
   HIP_TRY(hipMemcpyAsync(host, all, host_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return NBX_OK;
+}
+
+// sum m v^2 over the ranks from the partials their last step or kick left behind, added in rank order; synchronises every stream
+// of this process.  The caller has armed the watchdog: for a rank group this is a collective.
+int group_sum_mv2(nbx_group* g, double* out) {
+  double sum = 0.0;
+  if (g->my_rank >= 0) {
+    // one process per GPU: every rank reduces its partial on the device, one 8-byte all-gather, and all ranks add the values
+    nbx_ctx* c = g->rank[0];
+    NBX_TRY(use_device(c));
+    if (c->ke_parts > 0) NBX_TRY(enqueue_ke_reduce(c, 0));
+    else HIP_TRY(hipMemsetAsync(c->ke_dev, 0, sizeof(double), c->stream));
+    std::vector<double> parts((size_t)g->own.ranks);
+    NBX_TRY(gather_rows(g, c->ke_dev, sizeof(double), g->ke_all, parts.data(), sizeof(double) * parts.size(), "ncclAllGather(kenergy)"));
+    for (double p : parts) sum += p;
+  } else {
+    for (nbx_ctx* c : g->rank) {  // rank order: deterministic
+      double part = 0.0;
+      NBX_TRY(nbx_kenergy_partial(c, &part));
+      sum += part;
+    }
+    for (nbx_ctx* c : g->rank) NBX_TRY(nbx_sync(c));  // the exchange copies of the last step must have landed too
+  }
+  *out = sum;
   return NBX_OK;
 }
 
@@ -551,23 +577,7 @@ int nbx_group_step(nbx_group* g, double dt, int32_t nsteps, double* kenergy_out)
     double sum = 0.0;
     // the one place a stepping group blocks: every all-gather enqueued above completes only if every rank took part
     Watchdog::Scope bounded("nbx_group_step (position all-gathers + kinetic energy: stream synchronisation)", queued_allowance(g));
-    if (g->my_rank >= 0) {
-      // one process per GPU: every rank reduces its partial on the device, one 8-byte all-gather, and all ranks add the values
-      nbx_ctx* c = g->rank[0];
-      NBX_TRY(use_device(c));
-      if (c->ke_parts > 0) NBX_TRY(enqueue_ke_reduce(c, 0));
-      else HIP_TRY(hipMemsetAsync(c->ke_dev, 0, sizeof(double), c->stream));
-      std::vector<double> parts((size_t)g->own.ranks);
-      NBX_TRY(gather_rows(g, c->ke_dev, sizeof(double), g->ke_all, parts.data(), sizeof(double) * parts.size(), "ncclAllGather(kenergy)"));
-      for (double p : parts) sum += p;
-    } else {
-      for (nbx_ctx* c : g->rank) {  // rank order: deterministic
-        double part = 0.0;
-        NBX_TRY(nbx_kenergy_partial(c, &part));
-        sum += part;
-      }
-      for (nbx_ctx* c : g->rank) NBX_TRY(nbx_sync(c));  // the exchange copies of the last step must have landed too
-    }
+    NBX_TRY(group_sum_mv2(g, &sum));
     *kenergy_out = 0.5 * sum;
     if (window_from_sync && nsteps > 0)
       g->step_s_est = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_enter).count() / nsteps;
@@ -640,6 +650,28 @@ int nbx_group_diagnostics(nbx_group* g, nbx_diag_t* out) {
     }
   }
   diag_fill(sum, bodies, g->rank[0]->steps_done, out);
+  return NBX_OK;
+  });
+}
+
+// include/nbx_kick.h: every rank kicks its owned slice (nbx_kick.hip); positions do not move, so there is nothing to exchange
+int nbx_group_kick(nbx_group* g, double h, double* kenergy_out) {
+  return guarded("nbx_group_kick", [&]() -> int {
+  NBX_TRY(need(g, "nbx_group_kick", IS_THERE));
+  if (!std::isfinite(h)) return fail(NBX_ERR_ARG, "nbx_group_kick: h is not finite");
+  NBX_TRY(need(g, "nbx_group_kick", HAS_CONTEXTS | HAS_STATE));
+  for (const nbx_ctx* c : g->rank)  // before any rank is kicked: no rank may be left half a kick ahead of the others
+    if (c->pending_commit) return fail(NBX_ERR_STATE, "nbx_group_kick: a local step awaits nbx_commit");
+  g->steps_unsynced += 1;  // a kick is a force launch: queued work that the watchdog's allowance counts as a step's
+  for (nbx_ctx* c : g->rank) NBX_TRY(nbx_kick(c, h, nullptr));
+  if (kenergy_out) {
+    double sum = 0.0;
+    // as nbx_group_step: the one place the call blocks, and for a rank group a collective
+    Watchdog::Scope bounded("nbx_group_kick (kinetic energy: stream synchronisation)", queued_allowance(g));
+    Synced synced{g};
+    NBX_TRY(group_sum_mv2(g, &sum));
+    *kenergy_out = 0.5 * sum;
+  }
   return NBX_OK;
   });
 }

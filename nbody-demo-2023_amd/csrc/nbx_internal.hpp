@@ -1,5 +1,5 @@
 // nbx_internal.hpp -- the context object and what the translation units that serve it share (nbx_api.hip, nbx_group.hip,
-// nbx_diag.hip).  What a context has in common with the batch objects -- error plumbing, most of its fields, device choice,
+// nbx_diag.hip, nbx_kick.hip).  What a context has in common with the batch objects -- error plumbing, most of its fields, device choice,
 // profiling, the shared part of create and destroy -- is nbx_object.hpp.  Not part of the C-ABI (include/nbx.h is); nothing
 // here is visible outside the library.
 #pragma once
@@ -30,6 +30,9 @@ namespace nbx_detail {
 // shared by the context entry points (nbx_api.hip) and the groups (nbx_group.hip)
 double model_force_cost(const nbx_ctx* c, int own);  // relative cost of one force launch if the context owned `own` bodies (the tuner's predictor)
 int enqueue_ke_reduce(nbx_ctx* c, int slot);  // ke_part[0 .. ke_parts) -> ke_dev[slot], fixed order, on the context's stream
+// nbx_api.hip, for nbx_kick.hip: nbx_accel's acc-only force launch on the context's stream, outside the profile of the force kernel;
+// accp then holds plan.S slabs of own_pad records once the stream gets there.  The caller has checked the state and chosen the device.
+int enqueue_accel_slabs(nbx_ctx* c);
 constexpr int kDiagFieldCount = 9;  // = nbx::kDiagFields (nbx_diag_kernels.hpp; checked in nbx_diag.hip)
 // nbx_diag.hip: checks the context's state, then enqueues the diagnostics kernels on its stream; c->diag_dev then holds the
 // kDiagFields raw sums (nbx_diag_kernels.hpp) once the stream gets there

@@ -4,7 +4,8 @@
 // ensemble_step_kernel / ensemble_step_kernel_f64 (many systems per launch, nbx_ensemble.hip), nbx_ragged_kernels.hpp into
 // ragged_step_kernel / ragged_step_kernel_f64 (systems of different size per launch, nbx_ragged.hip).  The workgroup index is an
 // argument: a context passes blockIdx.x, an ensemble too -- after it has pointed the arguments at member blockIdx.y -- and a
-// ragged ensemble the index its work list gives workgroup blockIdx.x within its member.
+// ragged ensemble the index its work list gives workgroup blockIdx.x within its member.  nbx_batch_accel_kernels.hpp and
+// nbx_kick_kernels.hpp wrap the same bodies for the accelerations and the kicks of the members of either.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -46,9 +47,17 @@ struct ForceArgs {
 // ---------------------------------------------------------------------------------------------
 #include "nbx_jlane_loop.inc"
 
+// What lane t < NB does with body t's summed acceleration, as a compile-time choice:
+//   JLANE_EPI_ARG   what the argument acc_only says -- store it (nbx_accel) or integrate the body (a step); the default, and the
+//                   only form the step and accel kernels instantiate
+//   JLANE_EPI_KICK  the velocity half of the update alone (include/nbx_kick.h): v += a * a.dt, velm[li] stored, the position
+//                   neither advanced nor written, m v^2 of the kicked velocity into the workgroup's ke_part as a step does;
+//                   acc_only is not looked at, and neither of the other two epilogues is compiled in
+enum : int { JLANE_EPI_ARG = 0, JLANE_EPI_KICK = 1 };
+
 // LOOP_ASM (NB = 2, 4, 8): whole trips of 8 records per lane go through the generated loop, a remainder of four records
 // through the compiled one -- the same operations in the same order either way (tests compare the bits).
-template <int NB, int D, int LOOP>
+template <int NB, int D, int LOOP, int EPI = JLANE_EPI_ARG>
 __device__ __forceinline__ void jlane_step(const ForceArgs<float>& a, const int acc_only, const unsigned wg) {
   static_assert(NB % 2 == 0 && NB >= 2 && NB <= 16 && D >= 1, "two bodies per packed operation; body state must fit the SGPR file");
   static_assert(LOOP == LOOP_CXX || NB <= 8, "the generated loop exists for 2, 4 and 8 bodies per wave");
@@ -158,7 +167,10 @@ __device__ __forceinline__ void jlane_step(const ForceArgs<float>& a, const int 
       const float4 q = red[w][lane][l];
       sx += q.x; sy += q.y; sz += q.z;
     }
-    if (acc_only) {
+    if constexpr (EPI == JLANE_EPI_KICK) {
+      ke = (double)kick_update<float>(sx, sy, sz, a.dt, ve);
+      a.velm[li] = ve;
+    } else if (acc_only) {
       a.accp[li] = make_float4(sx, sy, sz, 0.f);
     } else {
       ke = (double)euler_update<float>(sx, sy, sz, a.dt, pe, ve);
@@ -168,13 +180,13 @@ __device__ __forceinline__ void jlane_step(const ForceArgs<float>& a, const int 
   }
   // one energy partial per workgroup, fixed order (wave shuffle tree, then the four waves)
   const double s = block_sum(ke, ksum);
-  if (threadIdx.x == 0 && !acc_only) a.ke_part[wg] = s;
+  if (threadIdx.x == 0 && (EPI == JLANE_EPI_KICK || !acc_only)) a.ke_part[wg] = s;
 }
 
 // The fp64 form of jlane_step: same decomposition (a wave owns NB bodies wave-uniformly, its lanes split j, LDS
 // transpose, the wave integrates its own bodies), plain fp64 arithmetic (pair<double>: there is no packed fp64), records
 // of 32 bytes.  NB <= 8: eight bodies are 48 SGPRs of coordinates.
-template <int NB, int D>
+template <int NB, int D, int EPI = JLANE_EPI_ARG>
 __device__ __forceinline__ void jlane_step_f64(const ForceArgs<double>& a, const int acc_only, const unsigned wg) {
   static_assert(NB >= 1 && NB <= 8 && D >= 1 && 64 * D <= kSgprOverread - 16, "body state must fit the SGPR file; the farthest request is D blocks past the array");
   __shared__ double4 red[4][NB][65];  // [wave][body][lane] + one column of padding (2080 B between the lanes that read)
@@ -239,7 +251,10 @@ __device__ __forceinline__ void jlane_step_f64(const ForceArgs<double>& a, const
       const double4 q = red[w][lane][l];
       sx += q.x; sy += q.y; sz += q.z;
     }
-    if (acc_only) {
+    if constexpr (EPI == JLANE_EPI_KICK) {
+      ke = kick_update<double>(sx, sy, sz, a.dt, ve);
+      a.velm[li] = ve;
+    } else if (acc_only) {
       a.accp[li] = make_double4(sx, sy, sz, 0.0);
     } else {
       ke = euler_update<double>(sx, sy, sz, a.dt, pe, ve);
@@ -248,7 +263,7 @@ __device__ __forceinline__ void jlane_step_f64(const ForceArgs<double>& a, const
     }
   }
   const double s = block_sum(ke, ksum);
-  if (threadIdx.x == 0 && !acc_only) a.ke_part[wg] = s;
+  if (threadIdx.x == 0 && (EPI == JLANE_EPI_KICK || !acc_only)) a.ke_part[wg] = s;
 }
 
 }  // namespace nbx

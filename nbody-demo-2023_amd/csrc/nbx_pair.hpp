@@ -169,4 +169,15 @@ __device__ __forceinline__ T euler_update(T ax, T ay, T az, T dt, typename V4<T>
   return mul_rn(v.w, v2);
 }
 
+// The velocity half of euler_update alone (include/nbx_kick.h): v += a*h with the same separately rounded operations, the
+// position untouched; returns the same term, m*(vx^2+vy^2+vz^2), of the kicked velocity.
+template <typename T>
+__device__ __forceinline__ T kick_update(T ax, T ay, T az, T h, typename V4<T>::type& v) {
+  v.x = add_rn(v.x, mul_rn(ax, h));
+  v.y = add_rn(v.y, mul_rn(ay, h));
+  v.z = add_rn(v.z, mul_rn(az, h));
+  const T v2 = add_rn(add_rn(mul_rn(v.x, v.x), mul_rn(v.y, v.y)), mul_rn(v.z, v.z));
+  return mul_rn(v.w, v2);
+}
+
 }  // namespace nbx

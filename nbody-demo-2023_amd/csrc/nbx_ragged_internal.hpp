@@ -1,5 +1,5 @@
 // nbx_ragged_internal.hpp -- the ragged-ensemble object, shared by the translation units that serve it: nbx_ragged.hip (create,
-// upload, step, download), nbx_ragged_diag.hip (diagnostics) and nbx_batch_accel.hip (accelerations).  Not part of the C-ABI (include/nbx_ragged.h is).  It names no
+// upload, step, download), nbx_ragged_diag.hip (diagnostics) nbx_batch_accel.hip (accelerations) and nbx_kick.hip (kicks).  Not part of the C-ABI (include/nbx_ragged.h is).  It names no
 // kernel header, so that each of these units compiles exactly the kernels it includes itself.  What a ragged ensemble has in
 // common with an ensemble -- most of its fields and all of its host plumbing -- is nbx_batch.hpp.
 #pragma once

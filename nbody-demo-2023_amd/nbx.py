@@ -52,6 +52,9 @@ RAGGED_DIAG_SYMBOLS = ("nbx_ragged_diagnostics",)
 # the symbols of include/nbx_batch_accel.h (the accelerations of the members of either kind in one launch), kept apart likewise
 BATCH_ACCEL_SYMBOLS = ("nbx_ensemble_accel", "nbx_ragged_accel")
 
+# the symbols of include/nbx_kick.h (velocity-only half steps for every kind of object), kept apart likewise
+KICK_SYMBOLS = ("nbx_kick", "nbx_ensemble_kick", "nbx_ragged_kick", "nbx_group_kick")
+
 
 class NbxError(RuntimeError):
     def __init__(self, code, where, text):
@@ -220,6 +223,11 @@ def load():
     if hasattr(L, "nbx_ensemble_accel"):  # likewise for nbx_batch_accel.hip
         L.nbx_ensemble_accel.argtypes = [vp, i32, i32, vp, vp, vp]
         L.nbx_ragged_accel.argtypes = [vp, i32, i32, vp, vp, vp]
+    if hasattr(L, "nbx_kick"):  # likewise for nbx_kick.hip
+        L.nbx_kick.argtypes = [vp, dbl, ctypes.POINTER(dbl)]
+        L.nbx_ensemble_kick.argtypes = [vp, dbl, vp]
+        L.nbx_ragged_kick.argtypes = [vp, dbl, vp]
+        L.nbx_group_kick.argtypes = [vp, dbl, ctypes.POINTER(dbl)]
     _lib = L
     return L
 
@@ -296,7 +304,24 @@ class _Handle:
             pass
 
 
-class Context(_Handle):
+def _need_kick(L, where):
+    if not hasattr(L, where):
+        raise NbxError(NBX_ERR_STATE, where, "%s was built without %s" % (LIB_PATH, where))
+
+
+class _Leapfrog:
+    """leapfrog() over a class's own kick() and step() (include/nbx_kick.h)."""
+
+    def leapfrog(self, nsteps, dt=DT, kenergy=True):
+        """kick(-dt/2); step(nsteps, dt); kick(+dt/2): kick-drift-kick leapfrog -- second order and time reversible, its steps
+        the plain step launches.  Positions and velocities are at the same time afterwards; the kinetic energy, if asked for, is
+        that of the final velocities."""
+        self.kick(-0.5 * dt)
+        self.step(nsteps, dt, kenergy=False)
+        return self.kick(0.5 * dt, kenergy)
+
+
+class Context(_Handle, _Leapfrog):
     """One nbx_ctx.  Keyword options are the nbx_opts fields."""
     _destroy = "nbx_destroy"
 
@@ -327,6 +352,14 @@ class Context(_Handle):
         ke = np.zeros(max(nsteps, 1), dtype=np.float64)
         _check(self._L.nbx_step_trace(self._h, dt, nsteps, _ptr(ke)), "nbx_step_trace")
         return ke[:nsteps]
+
+    def kick(self, h, kenergy=False):
+        """nbx_kick: v += a(x) * h for the owned bodies at the current positions; positions untouched.  The kinetic energy of the
+        kicked velocities if asked for (synchronises)."""
+        _need_kick(self._L, "nbx_kick")
+        ke = ctypes.c_double(0.0)
+        _check(self._L.nbx_kick(self._h, h, ctypes.byref(ke) if kenergy else None), "nbx_kick")
+        return ke.value if kenergy else None
 
     def step_local(self, dt=DT):
         _check(self._L.nbx_step_local(self._h, dt), "nbx_step_local")
@@ -376,7 +409,7 @@ class Context(_Handle):
         return d.asdict()
 
 
-class _Batch(_Handle):
+class _Batch(_Handle, _Leapfrog):
     """What Ensemble and Ragged share -- the library serves both from one host layer (csrc/nbx_batch.hpp), and every method here
     is the C-ABI call of that name under the class's prefix.  A subclass sets members and precision, calls _create, and adds
     upload and download, which differ in how the members' arrays are laid out."""
@@ -410,6 +443,14 @@ class _Batch(_Handle):
         ke = np.zeros((max(nsteps, 1), self.members), dtype=np.float64)
         self._call("step_trace", dt, nsteps, _ptr(ke))
         return ke[:nsteps]
+
+    def kick(self, h, kenergy=False):
+        """<prefix>_kick: v += a(x) * h for every body of every member at the current positions, one launch; positions untouched.
+        The kinetic energy of each member's kicked velocities (array of `members`) if asked for (synchronises)."""
+        _need_kick(self._L, self._prefix + "_kick")
+        ke = np.zeros(self.members, dtype=np.float64) if kenergy else None
+        self._call("kick", h, _ptr(ke))
+        return ke
 
     def sync(self):
         self._call("sync")
@@ -538,7 +579,7 @@ class Ragged(_Batch):
         return super().diagnostics(first, count)
 
 
-class Group(_Handle):
+class Group(_Handle, _Leapfrog):
     """One nbx_group: n_ranks contexts driven by this process (multi-GPU; logical ranks when devices repeat)."""
     _destroy = "nbx_group_destroy"
 
@@ -574,6 +615,14 @@ class Group(_Handle):
     def step(self, nsteps, dt=DT, kenergy=True):
         ke = ctypes.c_double(0.0)
         _check(self._L.nbx_group_step(self._h, dt, nsteps, ctypes.byref(ke) if kenergy else None), "nbx_group_step")
+        return ke.value if kenergy else None
+
+    def kick(self, h, kenergy=False):
+        """nbx_group_kick: every rank kicks its owned slice; with kenergy the ranks' sums are added as step() adds them
+        (collective for rank groups)."""
+        _need_kick(self._L, "nbx_group_kick")
+        ke = ctypes.c_double(0.0)
+        _check(self._L.nbx_group_kick(self._h, h, ctypes.byref(ke) if kenergy else None), "nbx_group_kick")
         return ke.value if kenergy else None
 
     def diagnostics(self):
