@@ -80,6 +80,9 @@ struct Object {
   // diagnostics (nbx_*diag.hip): per-workgroup partials and the reduced fields, allocated on first use
   double* diag_part = nullptr;
   double* diag_dev = nullptr;
+  // time scales (nbx_timescale.hip): per-workgroup rows of 3 and the reduced values per system, allocated on first use
+  double* ts_part = nullptr;
+  double* ts_dev = nullptr;
 };
 
 constexpr int kMaxProfiledLaunches = 8192;
@@ -278,7 +281,8 @@ inline void batch_quiesce(Object* o) {
 inline void batch_release(Object* o) {
   for (hipEvent_t ev : o->ev)
     if (ev) (void)hipEventDestroy(ev);
-  for (void* p : {o->posm[0], o->posm[1], o->velm, (void*)o->ke_part, (void*)o->ke_dev, (void*)o->diag_part, (void*)o->diag_dev})
+  for (void* p : {o->posm[0], o->posm[1], o->velm, (void*)o->ke_part, (void*)o->ke_dev, (void*)o->diag_part, (void*)o->diag_dev, (void*)o->ts_part,
+                  (void*)o->ts_dev})
     if (p) (void)hipFree(p);
   if (o->own_stream) (void)hipStreamDestroy(o->stream);
 }

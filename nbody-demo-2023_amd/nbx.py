@@ -5,6 +5,7 @@ the import of the library fails loudly, and without a HIP device nbx_create() re
 NBX_ERR_DEVICE which is raised as NbxError.
 """
 import ctypes
+import math
 import os
 import sys
 
@@ -55,6 +56,9 @@ BATCH_ACCEL_SYMBOLS = ("nbx_ensemble_accel", "nbx_ragged_accel")
 # the symbols of include/nbx_kick.h (velocity-only half steps for every kind of object), kept apart likewise
 KICK_SYMBOLS = ("nbx_kick", "nbx_ensemble_kick", "nbx_ragged_kick", "nbx_group_kick")
 
+# the symbols of include/nbx_timescale.h (pair approach and free-fall rates for choosing dt), kept apart likewise
+TIMESCALE_SYMBOLS = ("nbx_timescale", "nbx_ensemble_timescale", "nbx_ragged_timescale")
+
 
 class NbxError(RuntimeError):
     def __init__(self, code, where, text):
@@ -104,6 +108,17 @@ class Diag(ctypes.Structure):
         d["mass_moment"] = list(self.mass_moment)
         d["etotal"] = self.kenergy + self.potential
         return d
+
+
+class Timescale(ctypes.Structure):
+    """nbx_timescale_t (include/nbx_timescale.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("n", ctypes.c_int32), ("steps_done", ctypes.c_int64),
+        ("approach_rate2", ctypes.c_double), ("freefall_rate2", ctypes.c_double), ("min_r2", ctypes.c_double),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
 
 
 class EnsembleStats(ctypes.Structure):
@@ -228,6 +243,10 @@ def load():
         L.nbx_ensemble_kick.argtypes = [vp, dbl, vp]
         L.nbx_ragged_kick.argtypes = [vp, dbl, vp]
         L.nbx_group_kick.argtypes = [vp, dbl, ctypes.POINTER(dbl)]
+    if hasattr(L, "nbx_timescale"):  # likewise for nbx_timescale.hip
+        L.nbx_timescale.argtypes = [vp, ctypes.POINTER(Timescale)]
+        L.nbx_ensemble_timescale.argtypes = [vp, i32, i32, ctypes.POINTER(Timescale)]
+        L.nbx_ragged_timescale.argtypes = [vp, i32, i32, ctypes.POINTER(Timescale)]
     _lib = L
     return L
 
@@ -304,7 +323,7 @@ class _Handle:
             pass
 
 
-def _need_kick(L, where):
+def _need(L, where):
     if not hasattr(L, where):
         raise NbxError(NBX_ERR_STATE, where, "%s was built without %s" % (LIB_PATH, where))
 
@@ -321,7 +340,33 @@ class _Leapfrog:
         return self.kick(0.5 * dt, kenergy)
 
 
-class Context(_Handle, _Leapfrog):
+def suggest_dt(ts, eta):
+    """eta / sqrt(rate) with rate the largest approach_rate2 or freefall_rate2 of `ts` -- one dict of timescale() or a list of
+    them (the members of a batch object: the step all of them can take) -- or inf where every rate is 0."""
+    entries = [ts] if isinstance(ts, dict) else list(ts)
+    rate = max([max(t["approach_rate2"], t["freefall_rate2"]) for t in entries], default=0.0)
+    return eta / math.sqrt(rate) if rate > 0.0 else math.inf
+
+
+class _Adaptive:
+    """adaptive() over a class's own timescale() and step() (include/nbx_timescale.h)."""
+
+    def adaptive(self, t_end, eta, dt_max, max_steps=100000):
+        """Plain steps from t = 0 to t_end, each of dt = min(dt_max, suggest_dt(self.timescale(), eta), t_end - t): one
+        timescale call and one step call per turn, every member of a batch object taking the same dt, the smallest any member
+        asks for.  Returns (t, steps, dts) with t == t_end; RuntimeError if max_steps turns do not get there."""
+        t, dts = 0.0, []
+        while t < t_end:
+            if len(dts) >= max_steps:
+                raise RuntimeError("adaptive: t = %r of %r after max_steps = %d steps" % (t, t_end, max_steps))
+            dt = min(dt_max, suggest_dt(self.timescale(), eta), t_end - t)
+            self.step(1, dt, kenergy=False)
+            dts.append(dt)
+            t = t_end if dt == t_end - t else t + dt
+        return t, len(dts), dts
+
+
+class Context(_Handle, _Leapfrog, _Adaptive):
     """One nbx_ctx.  Keyword options are the nbx_opts fields."""
     _destroy = "nbx_destroy"
 
@@ -356,10 +401,19 @@ class Context(_Handle, _Leapfrog):
     def kick(self, h, kenergy=False):
         """nbx_kick: v += a(x) * h for the owned bodies at the current positions; positions untouched.  The kinetic energy of the
         kicked velocities if asked for (synchronises)."""
-        _need_kick(self._L, "nbx_kick")
+        _need(self._L, "nbx_kick")
         ke = ctypes.c_double(0.0)
         _check(self._L.nbx_kick(self._h, h, ctypes.byref(ke) if kenergy else None), "nbx_kick")
         return ke.value if kenergy else None
+
+    def timescale(self):
+        """nbx_timescale: approach_rate2, freefall_rate2 and min_r2 over all pairs of the current state (plus n and
+        steps_done); suggest_dt() turns them into a step.  Synchronises."""
+        _need(self._L, "nbx_timescale")
+        t = Timescale()
+        t.struct_size = ctypes.sizeof(Timescale)
+        _check(self._L.nbx_timescale(self._h, ctypes.byref(t)), "nbx_timescale")
+        return t.asdict()
 
     def step_local(self, dt=DT):
         _check(self._L.nbx_step_local(self._h, dt), "nbx_step_local")
@@ -409,7 +463,7 @@ class Context(_Handle, _Leapfrog):
         return d.asdict()
 
 
-class _Batch(_Handle, _Leapfrog):
+class _Batch(_Handle, _Leapfrog, _Adaptive):
     """What Ensemble and Ragged share -- the library serves both from one host layer (csrc/nbx_batch.hpp), and every method here
     is the C-ABI call of that name under the class's prefix.  A subclass sets members and precision, calls _create, and adds
     upload and download, which differ in how the members' arrays are laid out."""
@@ -447,7 +501,7 @@ class _Batch(_Handle, _Leapfrog):
     def kick(self, h, kenergy=False):
         """<prefix>_kick: v += a(x) * h for every body of every member at the current positions, one launch; positions untouched.
         The kinetic energy of each member's kicked velocities (array of `members`) if asked for (synchronises)."""
-        _need_kick(self._L, self._prefix + "_kick")
+        _need(self._L, self._prefix + "_kick")
         ke = np.zeros(self.members, dtype=np.float64) if kenergy else None
         self._call("kick", h, _ptr(ke))
         return ke
@@ -475,6 +529,18 @@ class _Batch(_Handle, _Leapfrog):
             d[k].struct_size = ctypes.sizeof(Diag)
         self._call("diagnostics", first, count, d)
         return [d[k].asdict() for k in range(max(count, 0))]
+
+    def timescale(self, first=0, count=None):
+        """<prefix>_timescale: one dict per member of [first, first + count) (default: all from `first`), each what
+        Context.timescale() returns for a context of the member's size holding its state -- the same bits; one launch for all of
+        them.  Synchronises."""
+        _need(self._L, self._prefix + "_timescale")
+        count = self.members - first if count is None else count
+        t = (Timescale * max(count, 1))()
+        for k in range(max(count, 0)):
+            t[k].struct_size = ctypes.sizeof(Timescale)
+        self._call("timescale", first, count, t)
+        return [t[k].asdict() for k in range(max(count, 0))]
 
     def _accel(self, first, count, arrs):
         """<prefix>_accel into three host arrays (None skips one).  Synchronises."""
@@ -620,7 +686,7 @@ class Group(_Handle, _Leapfrog):
     def kick(self, h, kenergy=False):
         """nbx_group_kick: every rank kicks its owned slice; with kenergy the ranks' sums are added as step() adds them
         (collective for rank groups)."""
-        _need_kick(self._L, "nbx_group_kick")
+        _need(self._L, "nbx_group_kick")
         ke = ctypes.c_double(0.0)
         _check(self._L.nbx_group_kick(self._h, h, ctypes.byref(ke) if kenergy else None), "nbx_group_kick")
         return ke.value if kenergy else None
