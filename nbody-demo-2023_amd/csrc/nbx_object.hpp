@@ -83,6 +83,14 @@ struct Object {
   // time scales (nbx_timescale.hip): per-workgroup rows of 3 and the reduced values per system, allocated on first use
   double* ts_part = nullptr;
   double* ts_dev = nullptr;
+  // field at caller-supplied points (nbx_field.hip): the packed points, the partial rows and the result records, allocated on
+  // first use and grown -- never shrunk -- when a larger call arrives (sizes in bytes); field_tab: a ragged ensemble's
+  // {pos_off, n} per member, built on first use and fixed for the object's life
+  void* field_pts = nullptr;
+  void* field_part = nullptr;
+  void* field_out = nullptr;
+  void* field_tab = nullptr;
+  size_t field_pts_cap = 0, field_part_cap = 0, field_out_cap = 0;
 };
 
 constexpr int kMaxProfiledLaunches = 8192;
@@ -282,7 +290,7 @@ inline void batch_release(Object* o) {
   for (hipEvent_t ev : o->ev)
     if (ev) (void)hipEventDestroy(ev);
   for (void* p : {o->posm[0], o->posm[1], o->velm, (void*)o->ke_part, (void*)o->ke_dev, (void*)o->diag_part, (void*)o->diag_dev, (void*)o->ts_part,
-                  (void*)o->ts_dev})
+                  (void*)o->ts_dev, o->field_pts, o->field_part, o->field_out, o->field_tab})
     if (p) (void)hipFree(p);
   if (o->own_stream) (void)hipStreamDestroy(o->stream);
 }

@@ -59,6 +59,10 @@ KICK_SYMBOLS = ("nbx_kick", "nbx_ensemble_kick", "nbx_ragged_kick", "nbx_group_k
 # the symbols of include/nbx_timescale.h (pair approach and free-fall rates for choosing dt), kept apart likewise
 TIMESCALE_SYMBOLS = ("nbx_timescale", "nbx_ensemble_timescale", "nbx_ragged_timescale")
 
+# the symbols of include/nbx_field.h (acceleration and potential at caller-supplied points), kept apart likewise
+FIELD_SYMBOLS = ("nbx_field", "nbx_ensemble_field", "nbx_ragged_field")
+FIELD_KEYS = ("acc_x", "acc_y", "acc_z", "phi")
+
 
 class NbxError(RuntimeError):
     def __init__(self, code, where, text):
@@ -247,6 +251,10 @@ def load():
         L.nbx_timescale.argtypes = [vp, ctypes.POINTER(Timescale)]
         L.nbx_ensemble_timescale.argtypes = [vp, i32, i32, ctypes.POINTER(Timescale)]
         L.nbx_ragged_timescale.argtypes = [vp, i32, i32, ctypes.POINTER(Timescale)]
+    if hasattr(L, "nbx_field"):  # likewise for nbx_field.hip
+        L.nbx_field.argtypes = [vp, i32] + [vp] * 7
+        L.nbx_ensemble_field.argtypes = [vp, i32, i32, i32] + [vp] * 7
+        L.nbx_ragged_field.argtypes = [vp, i32, i32, i32] + [vp] * 7
     _lib = L
     return L
 
@@ -415,6 +423,18 @@ class Context(_Handle, _Leapfrog, _Adaptive):
         _check(self._L.nbx_timescale(self._h, ctypes.byref(t)), "nbx_timescale")
         return t.asdict()
 
+    def field(self, px, py, pz):
+        """nbx_field: the acceleration and the potential of the resident bodies at the m points (px, py, pz) -- every body
+        counts, a point is not a body -- as {"acc_x", "acc_y", "acc_z", "phi"}, arrays of m.  Synchronises."""
+        _need(self._L, "nbx_field")
+        p = [np.ascontiguousarray(a, dtype=self.dtype) for a in (px, py, pz)]
+        if p[0].ndim != 1 or any(a.shape != p[0].shape for a in p):
+            raise NbxError(NBX_ERR_ARG, "array", "expected three arrays of one shape (m,), got %r" % ([a.shape for a in p],))
+        m = p[0].shape[0]
+        out = {k: np.zeros(m, dtype=self.dtype) for k in FIELD_KEYS}
+        _check(self._L.nbx_field(self._h, m, *[_ptr(a) for a in p], *[_ptr(out[k]) for k in FIELD_KEYS]), "nbx_field")
+        return out
+
     def step_local(self, dt=DT):
         _check(self._L.nbx_step_local(self._h, dt), "nbx_step_local")
 
@@ -541,6 +561,21 @@ class _Batch(_Handle, _Leapfrog, _Adaptive):
             t[k].struct_size = ctypes.sizeof(Timescale)
         self._call("timescale", first, count, t)
         return [t[k].asdict() for k in range(max(count, 0))]
+
+    def field(self, px, py, pz, first=0, count=None):
+        """<prefix>_field: the acceleration and the potential of members [first, first + count) (default: all from `first`), each
+        at its own m points -- px, py, pz of shape (count, m), row k the points of member first + k -- as {"acc_x", "acc_y",
+        "acc_z", "phi"}, arrays (count, m); for each member the bits Context.field() returns for a context of the member's size
+        holding its state and given the same points; one launch for all of them.  Synchronises."""
+        _need(self._L, self._prefix + "_field")
+        count = self.members - first if count is None else count
+        p = [np.ascontiguousarray(a, dtype=self.dtype) for a in (px, py, pz)]
+        if p[0].ndim != 2 or p[0].shape[0] != max(count, 0) or any(a.shape != p[0].shape for a in p):
+            raise NbxError(NBX_ERR_ARG, "array", "expected three arrays of shape (%d, m), got %r" % (max(count, 0), [a.shape for a in p]))
+        m = p[0].shape[1]
+        out = {k: np.zeros((max(count, 0), m), dtype=self.dtype) for k in FIELD_KEYS}
+        self._call("field", first, count, m, *[_ptr(a) for a in p], *[_ptr(out[k]) for k in FIELD_KEYS])
+        return out
 
     def _accel(self, first, count, arrs):
         """<prefix>_accel into three host arrays (None skips one).  Synchronises."""
