@@ -91,6 +91,12 @@ struct Object {
   void* field_out = nullptr;
   void* field_tab = nullptr;
   size_t field_pts_cap = 0, field_part_cap = 0, field_out_cap = 0;
+  // nearest neighbours and radius counts (nbx_neighbours.hip): the partial records and the result records, allocated on first
+  // use and grown likewise (sizes in bytes); nb_tab: a ragged ensemble's {pos_off, out_off, n} per member, built on first use
+  void* nb_part = nullptr;
+  void* nb_out = nullptr;
+  void* nb_tab = nullptr;
+  size_t nb_part_cap = 0, nb_out_cap = 0;
 };
 
 constexpr int kMaxProfiledLaunches = 8192;
@@ -290,7 +296,7 @@ inline void batch_release(Object* o) {
   for (hipEvent_t ev : o->ev)
     if (ev) (void)hipEventDestroy(ev);
   for (void* p : {o->posm[0], o->posm[1], o->velm, (void*)o->ke_part, (void*)o->ke_dev, (void*)o->diag_part, (void*)o->diag_dev, (void*)o->ts_part,
-                  (void*)o->ts_dev, o->field_pts, o->field_part, o->field_out, o->field_tab})
+                  (void*)o->ts_dev, o->field_pts, o->field_part, o->field_out, o->field_tab, o->nb_part, o->nb_out, o->nb_tab})
     if (p) (void)hipFree(p);
   if (o->own_stream) (void)hipStreamDestroy(o->stream);
 }

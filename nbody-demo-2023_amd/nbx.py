@@ -63,6 +63,10 @@ TIMESCALE_SYMBOLS = ("nbx_timescale", "nbx_ensemble_timescale", "nbx_ragged_time
 FIELD_SYMBOLS = ("nbx_field", "nbx_ensemble_field", "nbx_ragged_field")
 FIELD_KEYS = ("acc_x", "acc_y", "acc_z", "phi")
 
+# the symbols of include/nbx_neighbours.h (nearest neighbour and radius count of every body), kept apart likewise
+NEIGHBOUR_SYMBOLS = ("nbx_neighbours", "nbx_ensemble_neighbours", "nbx_ragged_neighbours")
+NEIGHBOUR_KEYS = ("index", "r2", "within")
+
 
 class NbxError(RuntimeError):
     def __init__(self, code, where, text):
@@ -255,6 +259,10 @@ def load():
         L.nbx_field.argtypes = [vp, i32] + [vp] * 7
         L.nbx_ensemble_field.argtypes = [vp, i32, i32, i32] + [vp] * 7
         L.nbx_ragged_field.argtypes = [vp, i32, i32, i32] + [vp] * 7
+    if hasattr(L, "nbx_neighbours"):  # likewise for nbx_neighbours.hip
+        L.nbx_neighbours.argtypes = [vp, dbl, vp, vp, vp]
+        L.nbx_ensemble_neighbours.argtypes = [vp, i32, i32, dbl, vp, vp, vp]
+        L.nbx_ragged_neighbours.argtypes = [vp, i32, i32, dbl, vp, vp, vp]
     _lib = L
     return L
 
@@ -334,6 +342,20 @@ class _Handle:
 def _need(L, where):
     if not hasattr(L, where):
         raise NbxError(NBX_ERR_STATE, where, "%s was built without %s" % (LIB_PATH, where))
+
+
+def _neighbour_arrays(shape, dtype, radius):
+    """The three result arrays of a *_neighbours call; within is None -- a NULL pointer to the library -- without a radius."""
+    return {"index": np.zeros(shape, dtype=np.int32), "r2": np.zeros(shape, dtype=dtype),
+            "within": None if radius is None else np.zeros(shape, dtype=np.int32)}
+
+
+def mutual_pairs(index):
+    """The (i, j), i < j, with index[i] == j and index[j] == i -- mutual nearest neighbours -- as a (k, 2) int array."""
+    index = np.asarray(index)
+    i = np.arange(index.shape[0])
+    ok = (index > i) & (index[np.clip(index, 0, None)] == i)
+    return np.stack([i[ok], index[ok]], axis=1).astype(np.int64).reshape(-1, 2)
 
 
 class _Leapfrog:
@@ -433,6 +455,15 @@ class Context(_Handle, _Leapfrog, _Adaptive):
         m = p[0].shape[0]
         out = {k: np.zeros(m, dtype=self.dtype) for k in FIELD_KEYS}
         _check(self._L.nbx_field(self._h, m, *[_ptr(a) for a in p], *[_ptr(out[k]) for k in FIELD_KEYS]), "nbx_field")
+        return out
+
+    def neighbours(self, radius=None):
+        """nbx_neighbours: for every body its nearest neighbour, the softened squared distance to it and the number of bodies
+        within `radius`, as {"index", "r2", "within"}, arrays of n (all n bodies, also for a sliced context).  within is None
+        when radius is None: the count is then neither asked for nor paid for.  Synchronises."""
+        _need(self._L, "nbx_neighbours")
+        out = _neighbour_arrays((self.n,), self.dtype, radius)
+        _check(self._L.nbx_neighbours(self._h, 0.0 if radius is None else radius, *[_ptr(out[k]) for k in NEIGHBOUR_KEYS]), "nbx_neighbours")
         return out
 
     def step_local(self, dt=DT):
@@ -620,6 +651,16 @@ class Ensemble(_Batch):
         self._accel(first, count, a)
         return a
 
+    def neighbours(self, radius=None, first=0, count=None):
+        """nbx_ensemble_neighbours: {"index", "r2", "within"}, arrays (count, n), of members [first, first + count) (default: all
+        from `first`) -- for each member the bits Context.neighbours() returns for a context of n bodies holding its state; one
+        launch for all of them.  within is None when radius is None.  Synchronises."""
+        _need(self._L, "nbx_ensemble_neighbours")
+        count = self.members - first if count is None else count
+        out = _neighbour_arrays((max(count, 0), self.n), self.dtype, radius)
+        self._call("neighbours", first, count, 0.0 if radius is None else radius, *[_ptr(out[k]) for k in NEIGHBOUR_KEYS])
+        return out
+
     def diagnostics(self, first=0, count=None):
         """nbx_ensemble_diagnostics: one dict per member of [first, first + count) (default: all from `first`), each what
         Context.diagnostics() returns for a context of n bodies holding that member's state -- the same bits; one launch for
@@ -672,6 +713,18 @@ class Ragged(_Batch):
         self._accel(first, count, flat)
         at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
         return [[a[at[k]:at[k + 1]].copy() for a in flat] for k in range(len(sizes))]
+
+    def neighbours(self, radius=None, first=0, count=None):
+        """nbx_ragged_neighbours: one {"index", "r2", "within"} per member of [first, first + count) (default: all from `first`),
+        arrays of sizes[k] -- the bits Context.neighbours() returns for a context of sizes[k] bodies holding that member's state;
+        one launch for all of them.  within is None when radius is None.  Synchronises."""
+        _need(self._L, "nbx_ragged_neighbours")
+        count = self.members - first if count is None else count
+        sizes = self._range(first, count)
+        flat = _neighbour_arrays((max(sum(sizes), 1),), self.dtype, radius)  # >= 1: _ptr wants an address, also for an empty range
+        self._call("neighbours", first, count, 0.0 if radius is None else radius, *[_ptr(flat[k]) for k in NEIGHBOUR_KEYS])
+        at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+        return [{k: None if flat[k] is None else flat[k][at[m]:at[m + 1]].copy() for k in NEIGHBOUR_KEYS} for m in range(len(sizes))]
 
     def diagnostics(self, first=0, count=None):
         """nbx_ragged_diagnostics: one dict per member of [first, first + count) (default: all from `first`), each what
