@@ -97,6 +97,12 @@ struct Object {
   void* nb_out = nullptr;
   void* nb_tab = nullptr;
   size_t nb_part_cap = 0, nb_out_cap = 0;
+  // pair counts within a list of radii (nbx_paircount.hip): the workgroup records and the results, allocated on first use and
+  // grown likewise (sizes in bytes); pc_tab: a ragged ensemble's {pos_off, n} per member, built on first use
+  void* pc_part = nullptr;
+  void* pc_out = nullptr;
+  void* pc_tab = nullptr;
+  size_t pc_part_cap = 0, pc_out_cap = 0;
 };
 
 constexpr int kMaxProfiledLaunches = 8192;
@@ -296,7 +302,8 @@ inline void batch_release(Object* o) {
   for (hipEvent_t ev : o->ev)
     if (ev) (void)hipEventDestroy(ev);
   for (void* p : {o->posm[0], o->posm[1], o->velm, (void*)o->ke_part, (void*)o->ke_dev, (void*)o->diag_part, (void*)o->diag_dev, (void*)o->ts_part,
-                  (void*)o->ts_dev, o->field_pts, o->field_part, o->field_out, o->field_tab, o->nb_part, o->nb_out, o->nb_tab})
+                  (void*)o->ts_dev, o->field_pts, o->field_part, o->field_out, o->field_tab, o->nb_part, o->nb_out, o->nb_tab, o->pc_part,
+                  o->pc_out, o->pc_tab})
     if (p) (void)hipFree(p);
   if (o->own_stream) (void)hipStreamDestroy(o->stream);
 }

@@ -67,6 +67,10 @@ FIELD_KEYS = ("acc_x", "acc_y", "acc_z", "phi")
 NEIGHBOUR_SYMBOLS = ("nbx_neighbours", "nbx_ensemble_neighbours", "nbx_ragged_neighbours")
 NEIGHBOUR_KEYS = ("index", "r2", "within")
 
+# the symbols of include/nbx_paircount.h (pairs within each of a list of radii), kept apart likewise
+PAIRCOUNT_SYMBOLS = ("nbx_paircount", "nbx_ensemble_paircount", "nbx_ragged_paircount")
+PAIRCOUNT_MAX_RADII = 256
+
 
 class NbxError(RuntimeError):
     def __init__(self, code, where, text):
@@ -263,6 +267,10 @@ def load():
         L.nbx_neighbours.argtypes = [vp, dbl, vp, vp, vp]
         L.nbx_ensemble_neighbours.argtypes = [vp, i32, i32, dbl, vp, vp, vp]
         L.nbx_ragged_neighbours.argtypes = [vp, i32, i32, dbl, vp, vp, vp]
+    if hasattr(L, "nbx_paircount"):  # likewise for nbx_paircount.hip
+        L.nbx_paircount.argtypes = [vp, i32, vp, vp]
+        L.nbx_ensemble_paircount.argtypes = [vp, i32, i32, i32, vp, vp]
+        L.nbx_ragged_paircount.argtypes = [vp, i32, i32, i32, vp, vp]
     _lib = L
     return L
 
@@ -348,6 +356,28 @@ def _neighbour_arrays(shape, dtype, radius):
     """The three result arrays of a *_neighbours call; within is None -- a NULL pointer to the library -- without a radius."""
     return {"index": np.zeros(shape, dtype=np.int32), "r2": np.zeros(shape, dtype=dtype),
             "within": None if radius is None else np.zeros(shape, dtype=np.int32)}
+
+
+def _batch_paircount(o, radii, first, count):
+    """paircount() of an Ensemble or a Ragged."""
+    _need(o._L, o._prefix + "_paircount")
+    count = o.members - first if count is None else count
+    r = _radii(radii)
+    out = np.zeros((max(count, 0), r.shape[0]), dtype=np.uint64)
+    o._call("paircount", first, count, r.shape[0], _ptr(r), _ptr(out) if out.size else None)
+    return out
+
+
+def _radii(radii):
+    """The radii of a *_paircount call as the contiguous array of doubles the library reads."""
+    return np.ascontiguousarray(np.atleast_1d(np.asarray(radii, dtype=np.float64)).reshape(-1))
+
+
+def shell_counts(counts):
+    """The pair-separation histogram of paircount()'s result for ASCENDING radii: element k is the number of pairs in the shell
+    (radii[k - 1], radii[k]], element 0 the pairs within radii[0]; along the last axis, same shape and dtype."""
+    counts = np.asarray(counts)
+    return np.diff(counts, axis=-1, prepend=counts.dtype.type(0))
 
 
 def mutual_pairs(index):
@@ -464,6 +494,16 @@ class Context(_Handle, _Leapfrog, _Adaptive):
         _need(self._L, "nbx_neighbours")
         out = _neighbour_arrays((self.n,), self.dtype, radius)
         _check(self._L.nbx_neighbours(self._h, 0.0 if radius is None else radius, *[_ptr(out[k]) for k in NEIGHBOUR_KEYS]), "nbx_neighbours")
+        return out
+
+    def paircount(self, radii):
+        """nbx_paircount: the number of pairs i < j with r2(i, j) <= h2 for each of `radii` (any order, at most 256), a
+        np.uint64 array of len(radii) -- of all n bodies, also for a sliced context; one pass over the pairs per 16 radii.
+        Synchronises."""
+        _need(self._L, "nbx_paircount")
+        r = _radii(radii)
+        out = np.zeros(r.shape[0], dtype=np.uint64)
+        _check(self._L.nbx_paircount(self._h, r.shape[0], _ptr(r), _ptr(out)), "nbx_paircount")
         return out
 
     def step_local(self, dt=DT):
@@ -661,6 +701,12 @@ class Ensemble(_Batch):
         self._call("neighbours", first, count, 0.0 if radius is None else radius, *[_ptr(out[k]) for k in NEIGHBOUR_KEYS])
         return out
 
+    def paircount(self, radii, first=0, count=None):
+        """nbx_ensemble_paircount: a np.uint64 array (count, len(radii)) of members [first, first + count) (default: all from
+        `first`) -- for each member the bits Context.paircount() returns for a context of n bodies holding its state; one launch
+        per 16 radii for all of them.  Synchronises."""
+        return _batch_paircount(self, radii, first, count)
+
     def diagnostics(self, first=0, count=None):
         """nbx_ensemble_diagnostics: one dict per member of [first, first + count) (default: all from `first`), each what
         Context.diagnostics() returns for a context of n bodies holding that member's state -- the same bits; one launch for
@@ -725,6 +771,12 @@ class Ragged(_Batch):
         self._call("neighbours", first, count, 0.0 if radius is None else radius, *[_ptr(flat[k]) for k in NEIGHBOUR_KEYS])
         at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
         return [{k: None if flat[k] is None else flat[k][at[m]:at[m + 1]].copy() for k in NEIGHBOUR_KEYS} for m in range(len(sizes))]
+
+    def paircount(self, radii, first=0, count=None):
+        """nbx_ragged_paircount: a np.uint64 array (count, len(radii)) of members [first, first + count) (default: all from
+        `first`) -- for each member the bits Context.paircount() returns for a context of sizes[k] bodies holding its state; one
+        launch per 16 radii for all of them.  Synchronises."""
+        return _batch_paircount(self, radii, first, count)
 
     def diagnostics(self, first=0, count=None):
         """nbx_ragged_diagnostics: one dict per member of [first, first + count) (default: all from `first`), each what
