@@ -126,6 +126,41 @@ def truth(state, points, precision):
     return {"acc": acc, "phi": (-w[0][rows], -w[1][rows])}
 
 
+def truth_at(state, points, precision):
+    """truth() without the detour through an augmented state, O(m n): the same sums, the n bodies as the only sources, in fp64
+    for fp32 values and np.longdouble for fp64 values (tests/test_large_shapes_cpu.py holds it against truth()).  For shapes
+    whose m^2 an augmented state cannot afford."""
+    wide = precision == 64
+    if wide and not F.HAVE_LONGDOUBLE:
+        return truth(state, points, precision)
+    dtype = np.longdouble if wide else np.float64
+    m = len(points[0])
+    x = [np.asarray(state[f]).astype(dtype) for f in POS]
+    p = [np.asarray(c).astype(dtype) for c in points]
+    g = gm_as_uploaded(state["mass"]).astype(dtype)
+    hi, lo, A = np.zeros((m, 3)), np.zeros((m, 3)), np.zeros(m)
+    phi_hi, phi_lo = np.zeros(m), np.zeros(m)
+
+    def split(s):
+        h = s.astype(np.float64)
+        return h, (s - h.astype(dtype)).astype(np.float64)
+
+    def chunk(ab):
+        a, b = ab
+        d = [x[c][None, :] - p[c][a:b, None] for c in range(3)]
+        r2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + dtype(EPS2)
+        w = g[None, :] / np.sqrt(r2)
+        phi_hi[a:b], phi_lo[a:b] = split(-w.sum(axis=1))
+        w /= r2
+        for c in range(3):
+            t = d[c] * w
+            hi[a:b, c], lo[a:b, c] = split(t.sum(axis=1))
+            A[a:b] = np.maximum(A[a:b], np.abs(t).sum(axis=1).astype(np.float64))
+
+    P._pmap(chunk, F._row_chunks(m, len(g)))
+    return {"acc": (hi, lo, A), "phi": (phi_hi, phi_lo)}
+
+
 def k_acc(acc, tr, precision):
     """K per point of accelerations (m, 3) (or three arrays of m); where A == 0 the value must be exactly 0 (K = 0, else inf)."""
     a = np.stack([np.asarray(c) for c in acc], axis=1) if isinstance(acc, (list, tuple)) else np.asarray(acc)

@@ -70,9 +70,11 @@ def pass_slots(nradii):
     return out
 
 
-def restate(state, radii, precision, fault=None):
+def restate(state, radii, precision, fault=None, finish_rows=None):
     """The same counts by the kernels' structure.  `fault`: one of FAULTS, planted.  "unused slot counted": the unused slots of a
-    pass carry h2 = +inf and the finish folds every slot of the pass onto the radii the pass holds (slot s onto s mod used)."""
+    pass carry h2 = +inf and the finish folds every slot of the pass onto the radii the pass holds (slot s onto s mod used).
+    finish_rows: a fault of its own -- the finish adds only the first finish_rows of the splits x columns records of a pass
+    (record split * columns + column), as a strided loop that stops after its first round would."""
     assert fault is None or fault in FAULTS, fault
     x = _x(state)
     n = len(x[0])
@@ -102,7 +104,10 @@ def restate(state, radii, precision, fault=None):
     out = np.zeros(len(radii), dtype=np.uint64)
     cols = columns - 1 if fault == "last column dropped by the finish" else columns
     for p, (first, used, E) in enumerate(passes):
-        total = parts[p, :, :cols, :].astype(np.uint64).sum(axis=(0, 1))
+        kept = parts[p, :, :cols, :].astype(np.uint64)
+        if finish_rows is not None:
+            kept = kept * (np.arange(splits)[:, None] * columns + np.arange(cols)[None, :] < finish_rows)[:, :, None].astype(np.uint64)
+        total = kept.sum(axis=(0, 1))
         for s in range(E if fault == "unused slot counted" else used):
             out[first + s % used] += total[s]
     return out if fault == "not halved" else out >> np.uint64(1)

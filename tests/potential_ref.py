@@ -296,8 +296,10 @@ class Restatement:
     def _finish(self, ts, m_own):
         return -0.5 * float(np.sum(m_own * ts.sum(axis=1)))
 
-    def total(self, mass, fault=None):
-        """The potential partial of the owned bodies for these masses (T values of all n bodies)."""
+    def total(self, mass, fault=None, finish_rows=None):
+        """The potential partial of the owned bodies for these masses (T values of all n bodies).  finish_rows: a fault of its
+        own -- the reduce adds only the first finish_rows of the splits x cols partial rows (row split * cols + column of
+        diag_shape), as a strided loop that stops after its first round would."""
         mass = np.asarray(mass, dtype=self.T)
         gm = self._gm(mass)
         name = fault[0] if fault else None
@@ -308,6 +310,10 @@ class Restatement:
         ts = np.stack(_pmap(lambda t: self._tile(t, gm, fault), range(self.tiles)), axis=1).astype(np.float64)
         if name == "last tile of the last split skipped":
             ts[:, -1] = 0.0
+        if finish_rows is not None:
+            cols, _, _, per = diag_shape(self.i_count, self.n)
+            row = (np.arange(self.tiles) // per)[None, :] * cols + (np.arange(self.i_count) // COL)[:, None]
+            ts = np.where(row < finish_rows, ts, 0.0)
         m_own = mass[self.i_begin:self.i_begin + self.i_count].astype(np.float64)
         if name == "velm read at the global index":  # velm is indexed locally; beyond its end the read finds no mass
             at = self.i_begin + np.arange(self.i_begin, self.i_begin + self.i_count)
