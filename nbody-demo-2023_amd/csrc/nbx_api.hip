@@ -151,6 +151,14 @@ int nbx_detail::enqueue_ke_reduce(nbx_ctx* c, int slot) {
 }
 // nbx_kick (nbx_kick.hip): the launch nbx_accel reads back -- the accelerations at posm[cur] into the S slabs of accp -- not timed
 int nbx_detail::enqueue_accel_slabs(nbx_ctx* c) { return enqueue_force(c, true, 0.0, false); }
+// nbx_tracers_step (nbx_tracers.hip): one turn of nbx_step's plain loop -- the step's own launches, then the buffer flip
+int nbx_detail::enqueue_one_step(nbx_ctx* c, double dt) {
+  const int rc = enqueue_step_any(c, dt);
+  if (rc) return rc;
+  c->cur ^= 1;
+  c->steps_done += 1;
+  return NBX_OK;
+}
 // the tuner's predictor: nbx_plan.hpp, force_cost
 double nbx_detail::model_force_cost(const nbx_ctx* c, int own) { return force_cost(c->plan, c->precision, c->prop.multiProcessorCount, own); }
 

@@ -33,6 +33,10 @@ int enqueue_ke_reduce(nbx_ctx* c, int slot);  // ke_part[0 .. ke_parts) -> ke_de
 // nbx_api.hip, for nbx_kick.hip: nbx_accel's acc-only force launch on the context's stream, outside the profile of the force kernel;
 // accp then holds plan.S slabs of own_pad records once the stream gets there.  The caller has checked the state and chosen the device.
 int enqueue_accel_slabs(nbx_ctx* c);
+// nbx_api.hip, for nbx_tracers.hip: one step of an unsliced context as nbx_step's plain loop enqueues it -- the step's launches on
+// the context's stream (timed like nbx_step's), then cur flipped and steps_done counted.  The caller has checked the state and
+// chosen the device.
+int enqueue_one_step(nbx_ctx* c, double dt);
 constexpr int kDiagFieldCount = 9;  // = nbx::kDiagFields (nbx_diag_kernels.hpp; checked in nbx_diag.hip)
 // nbx_diag.hip: checks the context's state, then enqueues the diagnostics kernels on its stream; c->diag_dev then holds the
 // kDiagFields raw sums (nbx_diag_kernels.hpp) once the stream gets there

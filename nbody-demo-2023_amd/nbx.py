@@ -71,6 +71,16 @@ NEIGHBOUR_KEYS = ("index", "r2", "within")
 PAIRCOUNT_SYMBOLS = ("nbx_paircount", "nbx_ensemble_paircount", "nbx_ragged_paircount")
 PAIRCOUNT_MAX_RADII = 256
 
+# the symbols of include/nbx_tracers.h (resident test particles that step with the bodies), kept apart likewise
+TRACER_SYMBOLS = (
+    "nbx_tracers_upload", "nbx_tracers_download", "nbx_tracers_count", "nbx_tracers_step", "nbx_tracers_kick",
+    "nbx_ensemble_tracers_upload", "nbx_ensemble_tracers_download", "nbx_ensemble_tracers_count", "nbx_ensemble_tracers_step",
+    "nbx_ensemble_tracers_kick",
+    "nbx_ragged_tracers_upload", "nbx_ragged_tracers_download", "nbx_ragged_tracers_count", "nbx_ragged_tracers_step",
+    "nbx_ragged_tracers_kick",
+)
+TRACER_MAX = 1 << 22  # tracers per object: members * m
+
 
 class NbxError(RuntimeError):
     def __init__(self, code, where, text):
@@ -271,6 +281,16 @@ def load():
         L.nbx_paircount.argtypes = [vp, i32, vp, vp]
         L.nbx_ensemble_paircount.argtypes = [vp, i32, i32, i32, vp, vp]
         L.nbx_ragged_paircount.argtypes = [vp, i32, i32, i32, vp, vp]
+    if hasattr(L, "nbx_tracers_step"):  # likewise for nbx_tracers.hip
+        L.nbx_tracers_upload.argtypes = [vp, i32] + [vp] * 6
+        L.nbx_tracers_download.argtypes = [vp] + [vp] * 6
+        for prefix in ("nbx", "nbx_ensemble", "nbx_ragged"):
+            if prefix != "nbx":
+                getattr(L, prefix + "_tracers_upload").argtypes = [vp, i32, i32, i32] + [vp] * 6
+                getattr(L, prefix + "_tracers_download").argtypes = [vp, i32, i32] + [vp] * 6
+            getattr(L, prefix + "_tracers_count").argtypes = [vp, ctypes.POINTER(i32)]
+            getattr(L, prefix + "_tracers_step").argtypes = [vp, dbl, i32, vp]
+            getattr(L, prefix + "_tracers_kick").argtypes = [vp, dbl]
     _lib = L
     return L
 
@@ -400,6 +420,58 @@ class _Leapfrog:
         return self.kick(0.5 * dt, kenergy)
 
 
+class _Tracers:
+    """The resident tracers of include/nbx_tracers.h over a class's own _tracers_call(name, *args) -- the C-ABI call
+    <prefix>_tracers_<name> on its handle -- and _tracers_range(first, count) -> (leading range arguments, array shape before m)."""
+
+    def tracers_upload(self, points, velocities, first=0):
+        """<prefix>_tracers_upload: points = (px, py, pz) and velocities = (vx, vy, vz), six arrays of one shape -- (m,) for a
+        context, (count, m) for members first, first + 1, ... of a batch object (row k the tracers of member first + k).  Replaces
+        the set; m == 0 removes it.  The first upload fixes m for a batch object.  Synchronises."""
+        a = [np.ascontiguousarray(x, dtype=self.dtype) for x in tuple(points) + tuple(velocities)]
+        lead, shape = self._tracers_range(first, a[0].shape[0] if a[0].ndim == 2 else None)
+        if len(a) != 6 or a[0].ndim != len(shape) + 1 or any(x.shape != a[0].shape for x in a):
+            raise NbxError(NBX_ERR_ARG, "array", "expected six arrays of one shape %s, got %r" % (shape + ("m",), [x.shape for x in a]))
+        self._tracers_call("upload", *lead, a[0].shape[-1], *[_ptr(x) for x in a])
+
+    def tracers_download(self, first=0, count=None):
+        """<prefix>_tracers_download: {"pos_x", ..., "vel_z"}, arrays (m,) for a context, (count, m) for members
+        [first, first + count) of a batch object (default: all from `first`).  Synchronises."""
+        lead, shape = self._tracers_range(first, count, default=True)
+        m = self.tracers_count()
+        out = {f: np.zeros(shape + (m,), dtype=self.dtype) for f in FIELDS[:6]}
+        self._tracers_call("download", *lead, *[_ptr(out[f]) for f in FIELDS[:6]])
+        return out
+
+    def tracers_count(self):
+        """<prefix>_tracers_count: tracers per system (0: none)."""
+        m = ctypes.c_int32(0)
+        self._tracers_call("count", ctypes.byref(m))
+        return m.value
+
+    def tracers_step(self, nsteps, dt=DT, kenergy=True):
+        """<prefix>_tracers_step: nsteps steps of the bodies -- the bits step() gives -- and of every tracer, each tracer step in
+        the field of the bodies before their step; the bodies' kinetic energy after the last one if asked for (synchronises)."""
+        batch = hasattr(self, "members")
+        ke = (np.zeros(self.members, dtype=np.float64) if batch else np.zeros(1, dtype=np.float64)) if kenergy else None
+        self._tracers_call("step", dt, nsteps, _ptr(ke))
+        return None if ke is None else ke if batch else float(ke[0])
+
+    def tracers_kick(self, h):
+        """<prefix>_tracers_kick: w += a(p) * h for every tracer at the bodies' current positions; tracer positions and the
+        bodies untouched.  Does not synchronise."""
+        self._tracers_call("kick", h)
+
+    def tracers_leapfrog(self, nsteps, dt=DT, kenergy=True):
+        """Kick-drift-kick leapfrog of the joint system: kick(-dt/2) on bodies and tracers, tracers_step(nsteps, dt), kick(+dt/2)
+        on both.  The bodies' kinetic energy of the final velocities if asked for."""
+        self.kick(-0.5 * dt)
+        self.tracers_kick(-0.5 * dt)
+        self.tracers_step(nsteps, dt, kenergy=False)
+        self.tracers_kick(0.5 * dt)
+        return self.kick(0.5 * dt, kenergy)
+
+
 def suggest_dt(ts, eta):
     """eta / sqrt(rate) with rate the largest approach_rate2 or freefall_rate2 of `ts` -- one dict of timescale() or a list of
     them (the members of a batch object: the step all of them can take) -- or inf where every rate is 0."""
@@ -426,7 +498,7 @@ class _Adaptive:
         return t, len(dts), dts
 
 
-class Context(_Handle, _Leapfrog, _Adaptive):
+class Context(_Handle, _Leapfrog, _Adaptive, _Tracers):
     """One nbx_ctx.  Keyword options are the nbx_opts fields."""
     _destroy = "nbx_destroy"
 
@@ -506,6 +578,16 @@ class Context(_Handle, _Leapfrog, _Adaptive):
         _check(self._L.nbx_paircount(self._h, r.shape[0], _ptr(r), _ptr(out)), "nbx_paircount")
         return out
 
+    def _tracers_call(self, name, *args):
+        where = "nbx_tracers_" + name
+        _need(self._L, where)
+        _check(getattr(self._L, where)(self._h, *args), where)
+
+    def _tracers_range(self, first, count, default=False):
+        if first != 0 or count is not None:
+            raise NbxError(NBX_ERR_ARG, "tracers", "a context has one system: no member range")
+        return (), ()
+
     def step_local(self, dt=DT):
         _check(self._L.nbx_step_local(self._h, dt), "nbx_step_local")
 
@@ -554,7 +636,7 @@ class Context(_Handle, _Leapfrog, _Adaptive):
         return d.asdict()
 
 
-class _Batch(_Handle, _Leapfrog, _Adaptive):
+class _Batch(_Handle, _Leapfrog, _Adaptive, _Tracers):
     """What Ensemble and Ragged share -- the library serves both from one host layer (csrc/nbx_batch.hpp), and every method here
     is the C-ABI call of that name under the class's prefix.  A subclass sets members and precision, calls _create, and adds
     upload and download, which differ in how the members' arrays are laid out."""
@@ -647,6 +729,17 @@ class _Batch(_Handle, _Leapfrog, _Adaptive):
         out = {k: np.zeros((max(count, 0), m), dtype=self.dtype) for k in FIELD_KEYS}
         self._call("field", first, count, m, *[_ptr(a) for a in p], *[_ptr(out[k]) for k in FIELD_KEYS])
         return out
+
+    def _tracers_call(self, name, *args):
+        _need(self._L, "%s_tracers_%s" % (self._prefix, name))
+        self._call("tracers_" + name, *args)
+
+    def _tracers_range(self, first, count, default=False):
+        if count is None:
+            if not default:
+                raise NbxError(NBX_ERR_ARG, "array", "expected arrays of shape (count, m)")
+            count = self.members - first
+        return (first, count), (max(count, 0),)
 
     def _accel(self, first, count, arrs):
         """<prefix>_accel into three host arrays (None skips one).  Synchronises."""
