@@ -103,6 +103,12 @@ struct Object {
   void* pc_out = nullptr;
   void* pc_tab = nullptr;
   size_t pc_part_cap = 0, pc_out_cap = 0;
+  // k nearest neighbours (nbx_knn.hip): the partial rows and the result rows, allocated on first use and grown likewise (sizes
+  // in bytes); knn_tab: a ragged ensemble's {pos_off, out_off, n} per member, built on first use
+  void* knn_part = nullptr;
+  void* knn_out = nullptr;
+  void* knn_tab = nullptr;
+  size_t knn_part_cap = 0, knn_out_cap = 0;
   // resident tracers (nbx_tracers.hip): tr_m per system (0: none), every system's {x, y, z, 0} position and velocity records
   // one system after the other, and the partial rows of the pair work ([systems][tr_rows][tr_m] records, buffers of their own:
   // not the field's scratch), allocated by the first upload and grown likewise (sizes in bytes); tr_have: per system, its
@@ -314,7 +320,7 @@ inline void batch_release(Object* o) {
     if (ev) (void)hipEventDestroy(ev);
   for (void* p : {o->posm[0], o->posm[1], o->velm, (void*)o->ke_part, (void*)o->ke_dev, (void*)o->diag_part, (void*)o->diag_dev, (void*)o->ts_part,
                   (void*)o->ts_dev, o->field_pts, o->field_part, o->field_out, o->field_tab, o->nb_part, o->nb_out, o->nb_tab, o->pc_part,
-                  o->pc_out, o->pc_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
+                  o->pc_out, o->pc_tab, o->knn_part, o->knn_out, o->knn_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
     if (p) (void)hipFree(p);
   if (o->own_stream) (void)hipStreamDestroy(o->stream);
 }

@@ -81,6 +81,12 @@ TRACER_SYMBOLS = (
 )
 TRACER_MAX = 1 << 22  # tracers per object: members * m
 
+# the symbols of include/nbx_knn.h (the k nearest neighbours of every body), kept apart likewise
+KNN_SYMBOLS = ("nbx_knn", "nbx_ensemble_knn", "nbx_ragged_knn")
+KNN_KEYS = ("index", "r2")
+KNN_MAX = 16
+EPS2 = float(np.float32(1e-3))  # the library's softening, squared: (float)1.e-3f, widened (what every r2 carries)
+
 
 class NbxError(RuntimeError):
     def __init__(self, code, where, text):
@@ -291,6 +297,10 @@ def load():
             getattr(L, prefix + "_tracers_count").argtypes = [vp, ctypes.POINTER(i32)]
             getattr(L, prefix + "_tracers_step").argtypes = [vp, dbl, i32, vp]
             getattr(L, prefix + "_tracers_kick").argtypes = [vp, dbl]
+    if hasattr(L, "nbx_knn"):  # likewise for nbx_knn.hip
+        L.nbx_knn.argtypes = [vp, i32, vp, vp]
+        L.nbx_ensemble_knn.argtypes = [vp, i32, i32, i32, vp, vp]
+        L.nbx_ragged_knn.argtypes = [vp, i32, i32, i32, vp, vp]
     _lib = L
     return L
 
@@ -376,6 +386,42 @@ def _neighbour_arrays(shape, dtype, radius):
     """The three result arrays of a *_neighbours call; within is None -- a NULL pointer to the library -- without a radius."""
     return {"index": np.zeros(shape, dtype=np.int32), "r2": np.zeros(shape, dtype=dtype),
             "within": None if radius is None else np.zeros(shape, dtype=np.int32)}
+
+
+def _knn_arrays(rows, k, dtype):
+    """The two result arrays of a *_knn call, `rows` rows of k (at least one element each: _ptr wants an address)."""
+    size = max(rows * min(max(int(k), 0), KNN_MAX), 1)  # a k the library refuses needs no room
+    return {"index": np.zeros(size, dtype=np.int32), "r2": np.zeros(size, dtype=dtype)}
+
+
+def local_density(knn, mass):
+    """The local density estimator of Casertano & Hut from a knn() result of k >= 2 columns and the bodies' masses, in fp64:
+    rho_i = (the masses of the first k - 1 neighbours, summed) / (4/3 pi d_k^3), d_k^2 = max(r2[i, k - 1] - eps^2, 0) the
+    unsoftened squared distance to the k-th neighbour.  A row with fill -- a body with fewer than k partners -- gives 0, and so
+    does a body whose k-th neighbour sits on it (d_k = 0)."""
+    index = np.asarray(knn["index"])
+    r2 = np.asarray(knn["r2"], dtype=np.float64)
+    mass = np.asarray(mass, dtype=np.float64)
+    if index.ndim != 2 or index.shape != r2.shape or index.shape[1] < 2 or mass.shape != index.shape[:1]:
+        raise NbxError(NBX_ERR_ARG, "local_density", "expected index and r2 of shape (n, k), k >= 2, and n masses")
+    k = index.shape[1]
+    full = (index >= 0).all(axis=1)
+    d2 = np.maximum(np.where(full, r2[:, k - 1], np.inf) - EPS2, 0.0)
+    inside = np.where(full[:, None], mass[np.clip(index[:, :k - 1], 0, None)], 0.0).sum(axis=1)
+    rho = np.zeros(index.shape[0])
+    ok = full & (d2 > 0.0)
+    rho[ok] = inside[ok] / (4.0 / 3.0 * np.pi * d2[ok] ** 1.5)
+    return rho
+
+
+def density_centre(x, y, z, rho):
+    """(centre[3], core_radius) of Casertano & Hut from positions and local_density()'s rho, in fp64:
+    centre = sum rho_i x_i / sum rho_i,  core_radius = sqrt(sum rho_i^2 |x_i - centre|^2 / sum rho_i^2)."""
+    p = np.stack([np.asarray(a, dtype=np.float64) for a in (x, y, z)], axis=1)
+    rho = np.asarray(rho, dtype=np.float64)
+    centre = (rho[:, None] * p).sum(axis=0) / rho.sum()
+    d2 = ((p - centre) ** 2).sum(axis=1)
+    return centre, float(np.sqrt((rho * rho * d2).sum() / (rho * rho).sum()))
 
 
 def _batch_paircount(o, radii, first, count):
@@ -567,6 +613,15 @@ class Context(_Handle, _Leapfrog, _Adaptive, _Tracers):
         out = _neighbour_arrays((self.n,), self.dtype, radius)
         _check(self._L.nbx_neighbours(self._h, 0.0 if radius is None else radius, *[_ptr(out[k]) for k in NEIGHBOUR_KEYS]), "nbx_neighbours")
         return out
+
+    def knn(self, k):
+        """nbx_knn: for every body its k nearest neighbours, ascending in (r2, index), and the softened squared distances to
+        them, as {"index": (n, k) int32, "r2": (n, k)} (all n bodies, also for a sliced context); entries a body has no partner
+        for are index -1, r2 +inf.  1 <= k <= KNN_MAX.  Synchronises."""
+        _need(self._L, "nbx_knn")
+        flat = _knn_arrays(self.n, k, self.dtype)
+        _check(self._L.nbx_knn(self._h, k, *[_ptr(flat[key]) for key in KNN_KEYS]), "nbx_knn")
+        return {key: flat[key][:self.n * k].reshape(self.n, k) for key in KNN_KEYS}
 
     def paircount(self, radii):
         """nbx_paircount: the number of pairs i < j with r2(i, j) <= h2 for each of `radii` (any order, at most 256), a
@@ -794,6 +849,17 @@ class Ensemble(_Batch):
         self._call("neighbours", first, count, 0.0 if radius is None else radius, *[_ptr(out[k]) for k in NEIGHBOUR_KEYS])
         return out
 
+    def knn(self, k, first=0, count=None):
+        """nbx_ensemble_knn: {"index", "r2"}, arrays (count, n, k), of members [first, first + count) (default: all from `first`)
+        -- for each member the bits Context.knn(k) returns for a context of n bodies holding its state; one launch for all of
+        them.  Synchronises."""
+        _need(self._L, "nbx_ensemble_knn")
+        count = self.members - first if count is None else count
+        rows = max(count, 0) * self.n
+        flat = _knn_arrays(rows, k, self.dtype)
+        self._call("knn", first, count, k, *[_ptr(flat[key]) for key in KNN_KEYS])
+        return {key: flat[key][:rows * k].reshape(max(count, 0), self.n, k) for key in KNN_KEYS}
+
     def paircount(self, radii, first=0, count=None):
         """nbx_ensemble_paircount: a np.uint64 array (count, len(radii)) of members [first, first + count) (default: all from
         `first`) -- for each member the bits Context.paircount() returns for a context of n bodies holding its state; one launch
@@ -864,6 +930,18 @@ class Ragged(_Batch):
         self._call("neighbours", first, count, 0.0 if radius is None else radius, *[_ptr(flat[k]) for k in NEIGHBOUR_KEYS])
         at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
         return [{k: None if flat[k] is None else flat[k][at[m]:at[m + 1]].copy() for k in NEIGHBOUR_KEYS} for m in range(len(sizes))]
+
+    def knn(self, k, first=0, count=None):
+        """nbx_ragged_knn: one {"index", "r2"} per member of [first, first + count) (default: all from `first`), arrays
+        (sizes[m], k) -- the bits Context.knn(k) returns for a context of sizes[m] bodies holding that member's state; one launch
+        for all of them.  Synchronises."""
+        _need(self._L, "nbx_ragged_knn")
+        count = self.members - first if count is None else count
+        sizes = self._range(first, count)
+        flat = _knn_arrays(sum(sizes), k, self.dtype)
+        self._call("knn", first, count, k, *[_ptr(flat[key]) for key in KNN_KEYS])
+        at = np.concatenate([[0], np.cumsum(sizes)]).astype(int) * max(int(k), 0)
+        return [{key: flat[key][at[m]:at[m + 1]].reshape(sizes[m], k).copy() for key in KNN_KEYS} for m in range(len(sizes))]
 
     def paircount(self, radii, first=0, count=None):
         """nbx_ragged_paircount: a np.uint64 array (count, len(radii)) of members [first, first + count) (default: all from
