@@ -109,6 +109,16 @@ struct Object {
   void* knn_out = nullptr;
   void* knn_tab = nullptr;
   size_t knn_part_cap = 0, knn_out_cap = 0;
+  // friends-of-friends groups (nbx_fof.hip): the staged {x, y, z, label} records, the split rows of a pass, the work arrays
+  // (labels, their successors, where a body's record is, the histogram, the changed words) and the results, allocated on first
+  // use and grown likewise (sizes in bytes); fof_tab: a ragged ensemble's {pos_off, out_off, rec_off, n} per member, built on
+  // first use
+  void* fof_rec = nullptr;
+  void* fof_part = nullptr;
+  void* fof_work = nullptr;
+  void* fof_out = nullptr;
+  void* fof_tab = nullptr;
+  size_t fof_rec_cap = 0, fof_part_cap = 0, fof_work_cap = 0, fof_out_cap = 0;
   // resident tracers (nbx_tracers.hip): tr_m per system (0: none), every system's {x, y, z, 0} position and velocity records
   // one system after the other, and the partial rows of the pair work ([systems][tr_rows][tr_m] records, buffers of their own:
   // not the field's scratch), allocated by the first upload and grown likewise (sizes in bytes); tr_have: per system, its
@@ -320,7 +330,8 @@ inline void batch_release(Object* o) {
     if (ev) (void)hipEventDestroy(ev);
   for (void* p : {o->posm[0], o->posm[1], o->velm, (void*)o->ke_part, (void*)o->ke_dev, (void*)o->diag_part, (void*)o->diag_dev, (void*)o->ts_part,
                   (void*)o->ts_dev, o->field_pts, o->field_part, o->field_out, o->field_tab, o->nb_part, o->nb_out, o->nb_tab, o->pc_part,
-                  o->pc_out, o->pc_tab, o->knn_part, o->knn_out, o->knn_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
+                  o->pc_out, o->pc_tab, o->knn_part, o->knn_out, o->knn_tab, o->fof_rec, o->fof_part,
+                  o->fof_work, o->fof_out, o->fof_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
     if (p) (void)hipFree(p);
   if (o->own_stream) (void)hipStreamDestroy(o->stream);
 }

@@ -85,6 +85,11 @@ TRACER_MAX = 1 << 22  # tracers per object: members * m
 KNN_SYMBOLS = ("nbx_knn", "nbx_ensemble_knn", "nbx_ragged_knn")
 KNN_KEYS = ("index", "r2")
 KNN_MAX = 16
+
+# the symbols of include/nbx_fof.h (friends-of-friends groups of the resident bodies), kept apart likewise
+FOF_SYMBOLS = ("nbx_fof", "nbx_ensemble_fof", "nbx_ragged_fof")
+FOF_KEYS = ("label", "size", "groups", "largest", "passes")
+NBX_ERR_INTERNAL = -5  # include/nbx_fof.h: an invariant of the library did not hold
 EPS2 = float(np.float32(1e-3))  # the library's softening, squared: (float)1.e-3f, widened (what every r2 carries)
 
 
@@ -301,6 +306,10 @@ def load():
         L.nbx_knn.argtypes = [vp, i32, vp, vp]
         L.nbx_ensemble_knn.argtypes = [vp, i32, i32, i32, vp, vp]
         L.nbx_ragged_knn.argtypes = [vp, i32, i32, i32, vp, vp]
+    if hasattr(L, "nbx_fof"):  # likewise for nbx_fof.hip
+        L.nbx_fof.argtypes = [vp, dbl, vp, vp, vp, vp]
+        L.nbx_ensemble_fof.argtypes = [vp, i32, i32, dbl, vp, vp, vp, vp]
+        L.nbx_ragged_fof.argtypes = [vp, i32, i32, dbl, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -392,6 +401,33 @@ def _knn_arrays(rows, k, dtype):
     """The two result arrays of a *_knn call, `rows` rows of k (at least one element each: _ptr wants an address)."""
     size = max(rows * min(max(int(k), 0), KNN_MAX), 1)  # a k the library refuses needs no room
     return {"index": np.zeros(size, dtype=np.int32), "r2": np.zeros(size, dtype=dtype)}
+
+
+def _fof_arrays(bodies, systems):
+    """The four result arrays of a *_fof call (at least one element each: _ptr wants an address): label and size per body,
+    {groups, largest} per system as an (systems, 2) int32 array -- nbx_fof_info_t's layout -- and the scalar passes."""
+    return [np.zeros(max(bodies, 1), dtype=np.int32), np.zeros(max(bodies, 1), dtype=np.int32),
+            np.zeros((max(systems, 1), 2), dtype=np.int32), np.zeros(1, dtype=np.int32)]
+
+
+def fof_catalogue(label, mass, x, y, z, min_members=2):
+    """The groups of one system from fof()'s label and the bodies' masses and positions, in fp64: for every group of at least
+    `min_members` bodies its label, members, mass and centre of mass, as {"label": (g,) int64, "members": (g,) int64, "mass":
+    (g,), "centre": (g, 3)}, ordered by (-members, label)."""
+    label = np.asarray(label, dtype=np.int64)
+    mass = np.asarray(mass, dtype=np.float64)
+    p = np.stack([np.asarray(a, dtype=np.float64) for a in (x, y, z)], axis=1)
+    if label.ndim != 1 or mass.shape != label.shape or p.shape != label.shape + (3,):
+        raise NbxError(NBX_ERR_ARG, "fof_catalogue", "expected label, mass, x, y and z of one shape (n,)")
+    names, inverse, members = np.unique(label, return_inverse=True, return_counts=True)
+    total = np.bincount(inverse, weights=mass, minlength=len(names))
+    moment = np.stack([np.bincount(inverse, weights=mass * p[:, a], minlength=len(names)) for a in range(3)], axis=1)
+    keep = members >= min_members
+    names, members, total, moment = names[keep], members[keep], total[keep], moment[keep]
+    order = np.lexsort((names, -members))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        centre = moment[order] / total[order][:, None]
+    return {"label": names[order].astype(np.int64), "members": members[order].astype(np.int64), "mass": total[order], "centre": centre}
 
 
 def local_density(knn, mass):
@@ -622,6 +658,15 @@ class Context(_Handle, _Leapfrog, _Adaptive, _Tracers):
         flat = _knn_arrays(self.n, k, self.dtype)
         _check(self._L.nbx_knn(self._h, k, *[_ptr(flat[key]) for key in KNN_KEYS]), "nbx_knn")
         return {key: flat[key][:self.n * k].reshape(self.n, k) for key in KNN_KEYS}
+
+    def fof(self, radius):
+        """nbx_fof: the friends-of-friends groups at linking length `radius`, as {"label": (n,) int32 -- the lowest index of the
+        body's group --, "size": (n,) int32, "groups", "largest", "passes"} (all n bodies, also for a sliced context).
+        Synchronises once per pass."""
+        _need(self._L, "nbx_fof")
+        label, size, info, passes = _fof_arrays(self.n, 1)
+        _check(self._L.nbx_fof(self._h, radius, _ptr(label), _ptr(size), _ptr(info), _ptr(passes)), "nbx_fof")
+        return {"label": label[:self.n], "size": size[:self.n], "groups": int(info[0, 0]), "largest": int(info[0, 1]), "passes": int(passes[0])}
 
     def paircount(self, radii):
         """nbx_paircount: the number of pairs i < j with r2(i, j) <= h2 for each of `radii` (any order, at most 256), a
@@ -860,6 +905,19 @@ class Ensemble(_Batch):
         self._call("knn", first, count, k, *[_ptr(flat[key]) for key in KNN_KEYS])
         return {key: flat[key][:rows * k].reshape(max(count, 0), self.n, k) for key in KNN_KEYS}
 
+    def fof(self, radius, first=0, count=None):
+        """nbx_ensemble_fof: {"label", "size"}, int32 arrays (count, n), {"groups", "largest"}, int32 arrays (count,), and
+        "passes", the call's, of members [first, first + count) (default: all from `first`) -- for each member the labels and
+        sizes Context.fof() returns for a context of n bodies holding its state; every pass is one launch for all of them.
+        Synchronises once per pass."""
+        _need(self._L, "nbx_ensemble_fof")
+        count = self.members - first if count is None else count
+        S = max(count, 0)
+        label, size, info, passes = _fof_arrays(S * self.n, S)
+        self._call("fof", first, count, radius, _ptr(label), _ptr(size), _ptr(info), _ptr(passes))
+        return {"label": label[:S * self.n].reshape(S, self.n), "size": size[:S * self.n].reshape(S, self.n), "groups": info[:S, 0].copy(),
+                "largest": info[:S, 1].copy(), "passes": int(passes[0])}
+
     def paircount(self, radii, first=0, count=None):
         """nbx_ensemble_paircount: a np.uint64 array (count, len(radii)) of members [first, first + count) (default: all from
         `first`) -- for each member the bits Context.paircount() returns for a context of n bodies holding its state; one launch
@@ -942,6 +1000,20 @@ class Ragged(_Batch):
         self._call("knn", first, count, k, *[_ptr(flat[key]) for key in KNN_KEYS])
         at = np.concatenate([[0], np.cumsum(sizes)]).astype(int) * max(int(k), 0)
         return [{key: flat[key][at[m]:at[m + 1]].reshape(sizes[m], k).copy() for key in KNN_KEYS} for m in range(len(sizes))]
+
+    def fof(self, radius, first=0, count=None):
+        """nbx_ragged_fof: one {"label", "size", "groups", "largest", "passes"} per member of [first, first + count) (default:
+        all from `first`), label and size int32 arrays of sizes[m] -- what Context.fof() returns for a context of sizes[m]
+        bodies holding that member's state, but for "passes", which is the call's: the largest of the members' own; every pass
+        is one launch for all of them.  Synchronises once per pass."""
+        _need(self._L, "nbx_ragged_fof")
+        count = self.members - first if count is None else count
+        sizes = self._range(first, count)
+        label, size, info, passes = _fof_arrays(sum(sizes), len(sizes))
+        self._call("fof", first, count, radius, _ptr(label), _ptr(size), _ptr(info), _ptr(passes))
+        at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+        return [{"label": label[at[m]:at[m + 1]].copy(), "size": size[at[m]:at[m + 1]].copy(), "groups": int(info[m, 0]),
+                 "largest": int(info[m, 1]), "passes": int(passes[0])} for m in range(len(sizes))]
 
     def paircount(self, radii, first=0, count=None):
         """nbx_ragged_paircount: a np.uint64 array (count, len(radii)) of members [first, first + count) (default: all from
