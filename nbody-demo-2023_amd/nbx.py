@@ -92,6 +92,11 @@ FOF_KEYS = ("label", "size", "groups", "largest", "passes")
 NBX_ERR_INTERNAL = -5  # include/nbx_fof.h: an invariant of the library did not hold
 EPS2 = float(np.float32(1e-3))  # the library's softening, squared: (float)1.e-3f, widened (what every r2 carries)
 
+# the symbols of include/nbx_binaries.h (most bound partner and bound count of every body), kept apart likewise
+BINARIES_SYMBOLS = ("nbx_binaries", "nbx_ensemble_binaries", "nbx_ragged_binaries")
+BINARIES_KEYS = ("partner", "energy", "bound")
+GRAV = float(np.float32(6.67259e-11))  # the library's G: (float)6.67259e-11f, widened
+
 
 class NbxError(RuntimeError):
     def __init__(self, code, where, text):
@@ -310,6 +315,10 @@ def load():
         L.nbx_fof.argtypes = [vp, dbl, vp, vp, vp, vp]
         L.nbx_ensemble_fof.argtypes = [vp, i32, i32, dbl, vp, vp, vp, vp]
         L.nbx_ragged_fof.argtypes = [vp, i32, i32, dbl, vp, vp, vp, vp]
+    if hasattr(L, "nbx_binaries"):  # likewise for nbx_binaries.hip
+        L.nbx_binaries.argtypes = [vp, vp, vp, vp]
+        L.nbx_ensemble_binaries.argtypes = [vp, i32, i32, vp, vp, vp]
+        L.nbx_ragged_binaries.argtypes = [vp, i32, i32, vp, vp, vp]
     _lib = L
     return L
 
@@ -408,6 +417,46 @@ def _fof_arrays(bodies, systems):
     {groups, largest} per system as an (systems, 2) int32 array -- nbx_fof_info_t's layout -- and the scalar passes."""
     return [np.zeros(max(bodies, 1), dtype=np.int32), np.zeros(max(bodies, 1), dtype=np.int32),
             np.zeros((max(systems, 1), 2), dtype=np.int32), np.zeros(1, dtype=np.int32)]
+
+
+def _binaries_arrays(shape, dtype, bound):
+    """The three result arrays of a *_binaries call; bound is None -- a NULL pointer to the library -- where it is not asked for."""
+    return {"partner": np.zeros(shape, dtype=np.int32), "energy": np.zeros(shape, dtype=dtype),
+            "bound": np.zeros(shape, dtype=np.int32) if bound else None}
+
+
+def binary_catalogue(partner, energy, mass, x, y, z, vx, vy, vz):
+    """The mutual bound pairs of one system from binaries()'s partner and energy and the bodies' masses, positions and
+    velocities: the (i, j), i < j, with partner[i] == j, partner[j] == i and energy[i] < 0, and their Kepler elements in fp64,
+    as {"i", "j": (k,) int64, "energy": the specific two-body energy |dv|^2 / 2 - G (m_i + m_j) / |dx|, "a": the semi-major axis
+    -G (m_i + m_j) / (2 energy), "ecc": the eccentricity sqrt(1 + 2 energy h^2 / (G (m_i + m_j))^2) from the specific angular
+    momentum h = |dx x dv|, "period": 2 pi sqrt(a^3 / (G (m_i + m_j))), "binding": the binding energy mu |energy|, mu = m_i m_j /
+    (m_i + m_j)}, sorted by binding energy, descending (then by i).  The elements IGNORE THE SOFTENING: the pairs are chosen by
+    the library's softened energy, their elements are those of the unsoftened two-body problem, evaluated here from the state
+    (the softened energy is never below it, so a pair the library calls bound is bound here too); two bodies at one position
+    give a = 0."""
+    partner = np.asarray(partner, dtype=np.int64)
+    energy = np.asarray(energy, dtype=np.float64)
+    mass = np.asarray(mass, dtype=np.float64)
+    p = np.stack([np.asarray(a, dtype=np.float64) for a in (x, y, z)], axis=-1)
+    v = np.stack([np.asarray(a, dtype=np.float64) for a in (vx, vy, vz)], axis=-1)
+    if partner.ndim != 1 or energy.shape != partner.shape or mass.shape != partner.shape or p.shape != partner.shape + (3,) or v.shape != p.shape:
+        raise NbxError(NBX_ERR_ARG, "binary_catalogue", "expected partner, energy, mass, x, y, z, vx, vy and vz of one shape (n,)")
+    idx = np.arange(partner.shape[0])
+    ok = (partner > idx) & (partner[np.clip(partner, 0, None)] == idx) & (energy < 0.0)
+    i, j = idx[ok], partner[ok]
+    dx, dv = p[j] - p[i], v[j] - v[i]
+    gm = GRAV * (mass[i] + mass[j])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        e = 0.5 * (dv * dv).sum(axis=1) - gm / np.sqrt((dx * dx).sum(axis=1))
+        a = -gm / (2.0 * e)
+        h = np.cross(dx, dv)
+        ecc = np.sqrt(np.maximum(1.0 + 2.0 * e * (h * h).sum(axis=1) / (gm * gm), 0.0))
+        period = 2.0 * np.pi * np.sqrt(a * a * a / gm)
+        binding = mass[i] * mass[j] / (mass[i] + mass[j]) * np.abs(e)
+    order = np.lexsort((i, -binding))
+    return {"i": i[order], "j": j[order], "energy": e[order], "a": a[order], "ecc": ecc[order], "period": period[order],
+            "binding": binding[order]}
 
 
 def fof_catalogue(label, mass, x, y, z, min_members=2):
@@ -659,6 +708,15 @@ class Context(_Handle, _Leapfrog, _Adaptive, _Tracers):
         _check(self._L.nbx_knn(self._h, k, *[_ptr(flat[key]) for key in KNN_KEYS]), "nbx_knn")
         return {key: flat[key][:self.n * k].reshape(self.n, k) for key in KNN_KEYS}
 
+    def binaries(self, bound=True):
+        """nbx_binaries: for every body its most bound partner, the specific two-body energy of that pair and the number of
+        bodies it is bound to, as {"partner", "energy", "bound"}, arrays of n.  bound is None when bound=False: the count is then
+        neither asked for nor paid for.  A sliced context is refused.  Synchronises."""
+        _need(self._L, "nbx_binaries")
+        out = _binaries_arrays((self.n,), self.dtype, bound)
+        _check(self._L.nbx_binaries(self._h, *[_ptr(out[k]) for k in BINARIES_KEYS]), "nbx_binaries")
+        return out
+
     def fof(self, radius):
         """nbx_fof: the friends-of-friends groups at linking length `radius`, as {"label": (n,) int32 -- the lowest index of the
         body's group --, "size": (n,) int32, "groups", "largest", "passes"} (all n bodies, also for a sliced context).
@@ -905,6 +963,16 @@ class Ensemble(_Batch):
         self._call("knn", first, count, k, *[_ptr(flat[key]) for key in KNN_KEYS])
         return {key: flat[key][:rows * k].reshape(max(count, 0), self.n, k) for key in KNN_KEYS}
 
+    def binaries(self, bound=True, first=0, count=None):
+        """nbx_ensemble_binaries: {"partner", "energy", "bound"}, arrays (count, n), of members [first, first + count) (default:
+        all from `first`) -- for each member the bits Context.binaries() returns for a context of n bodies holding its state; one
+        launch for all of them.  bound is None when bound=False.  Synchronises."""
+        _need(self._L, "nbx_ensemble_binaries")
+        count = self.members - first if count is None else count
+        out = _binaries_arrays((max(count, 0), self.n), self.dtype, bound)
+        self._call("binaries", first, count, *[_ptr(out[k]) for k in BINARIES_KEYS])
+        return out
+
     def fof(self, radius, first=0, count=None):
         """nbx_ensemble_fof: {"label", "size"}, int32 arrays (count, n), {"groups", "largest"}, int32 arrays (count,), and
         "passes", the call's, of members [first, first + count) (default: all from `first`) -- for each member the labels and
@@ -1000,6 +1068,18 @@ class Ragged(_Batch):
         self._call("knn", first, count, k, *[_ptr(flat[key]) for key in KNN_KEYS])
         at = np.concatenate([[0], np.cumsum(sizes)]).astype(int) * max(int(k), 0)
         return [{key: flat[key][at[m]:at[m + 1]].reshape(sizes[m], k).copy() for key in KNN_KEYS} for m in range(len(sizes))]
+
+    def binaries(self, bound=True, first=0, count=None):
+        """nbx_ragged_binaries: one {"partner", "energy", "bound"} per member of [first, first + count) (default: all from
+        `first`), arrays of sizes[k] -- the bits Context.binaries() returns for a context of sizes[k] bodies holding that member's
+        state, partner member-local; one launch for all of them.  bound is None when bound=False.  Synchronises."""
+        _need(self._L, "nbx_ragged_binaries")
+        count = self.members - first if count is None else count
+        sizes = self._range(first, count)
+        flat = _binaries_arrays((max(sum(sizes), 1),), self.dtype, bound)  # >= 1: _ptr wants an address, also for an empty range
+        self._call("binaries", first, count, *[_ptr(flat[k]) for k in BINARIES_KEYS])
+        at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+        return [{k: None if flat[k] is None else flat[k][at[m]:at[m + 1]].copy() for k in BINARIES_KEYS} for m in range(len(sizes))]
 
     def fof(self, radius, first=0, count=None):
         """nbx_ragged_fof: one {"label", "size", "groups", "largest", "passes"} per member of [first, first + count) (default:
