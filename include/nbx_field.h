@@ -69,9 +69,10 @@
  * Unspecified results: a coordinate of a point that is not finite, or whose square overflows T, gives unspecified values for
  * that point only.
  *
- * Deliberately not here: groups; device pointers for points or results; tidal tensors or jerk; self-exclusion by index (take
- * the identities above); the reference summation order; hipGraph replay; a command-line word or an environment knob in nbody.x
- * (its output is the reference's).
+ * Deliberately not here: groups; device pointers for points or results; jerk; self-exclusion by index (take the identities
+ * above); the reference summation order; hipGraph replay; a command-line word or an environment knob in nbody.x (its output is
+ * the reference's).  This list used to say "tidal tensors or jerk": the tidal tensor, the second derivative of the potential
+ * at points or at the bodies, is now nbx_tidal.h; jerk stays out.
  */
 #ifndef NBX_FIELD_H
 #define NBX_FIELD_H

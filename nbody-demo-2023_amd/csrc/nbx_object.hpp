@@ -126,6 +126,14 @@ struct Object {
   void* bin_out = nullptr;
   void* bin_tab = nullptr;
   size_t bin_part_cap = 0, bin_out_cap = 0;
+  // tidal tensors at caller-supplied points and at the bodies (nbx_tidal.hip): the packed points, the partial rows (two records
+  // per point and split) and the result records (two per point), allocated on first use and grown likewise (sizes in bytes);
+  // tidal_tab: a ragged ensemble's {pos_off, out_off, n} per member, built on first use
+  void* tidal_pts = nullptr;
+  void* tidal_part = nullptr;
+  void* tidal_out = nullptr;
+  void* tidal_tab = nullptr;
+  size_t tidal_pts_cap = 0, tidal_part_cap = 0, tidal_out_cap = 0;
   // resident tracers (nbx_tracers.hip): tr_m per system (0: none), every system's {x, y, z, 0} position and velocity records
   // one system after the other, and the partial rows of the pair work ([systems][tr_rows][tr_m] records, buffers of their own:
   // not the field's scratch), allocated by the first upload and grown likewise (sizes in bytes); tr_have: per system, its
@@ -338,7 +346,8 @@ inline void batch_release(Object* o) {
   for (void* p : {o->posm[0], o->posm[1], o->velm, (void*)o->ke_part, (void*)o->ke_dev, (void*)o->diag_part, (void*)o->diag_dev, (void*)o->ts_part,
                   (void*)o->ts_dev, o->field_pts, o->field_part, o->field_out, o->field_tab, o->nb_part, o->nb_out, o->nb_tab, o->pc_part,
                   o->pc_out, o->pc_tab, o->knn_part, o->knn_out, o->knn_tab, o->fof_rec, o->fof_part,
-                  o->fof_work, o->fof_out, o->fof_tab, o->bin_part, o->bin_out, o->bin_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
+                  o->fof_work, o->fof_out, o->fof_tab, o->bin_part, o->bin_out, o->bin_tab, o->tidal_pts, o->tidal_part,
+                  o->tidal_out, o->tidal_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
     if (p) (void)hipFree(p);
   if (o->own_stream) (void)hipStreamDestroy(o->stream);
 }

@@ -95,6 +95,10 @@ EPS2 = float(np.float32(1e-3))  # the library's softening, squared: (float)1.e-3
 # the symbols of include/nbx_binaries.h (most bound partner and bound count of every body), kept apart likewise
 BINARIES_SYMBOLS = ("nbx_binaries", "nbx_ensemble_binaries", "nbx_ragged_binaries")
 BINARIES_KEYS = ("partner", "energy", "bound")
+# the symbols of include/nbx_tidal.h (the tidal tensor at caller-supplied points and at the bodies), kept apart likewise
+TIDAL_SYMBOLS = ("nbx_tidal", "nbx_ensemble_tidal", "nbx_ragged_tidal",
+                 "nbx_tidal_bodies", "nbx_ensemble_tidal_bodies", "nbx_ragged_tidal_bodies")
+TIDAL_KEYS = ("t_xx", "t_xy", "t_xz", "t_yy", "t_yz", "t_zz")
 GRAV = float(np.float32(6.67259e-11))  # the library's G: (float)6.67259e-11f, widened
 
 
@@ -319,6 +323,13 @@ def load():
         L.nbx_binaries.argtypes = [vp, vp, vp, vp]
         L.nbx_ensemble_binaries.argtypes = [vp, i32, i32, vp, vp, vp]
         L.nbx_ragged_binaries.argtypes = [vp, i32, i32, vp, vp, vp]
+    if hasattr(L, "nbx_tidal"):  # likewise for nbx_tidal.hip
+        L.nbx_tidal.argtypes = [vp, i32, vp, vp, vp, vp]
+        L.nbx_ensemble_tidal.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+        L.nbx_ragged_tidal.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+        L.nbx_tidal_bodies.argtypes = [vp, vp]
+        L.nbx_ensemble_tidal_bodies.argtypes = [vp, i32, i32, vp]
+        L.nbx_ragged_tidal_bodies.argtypes = [vp, i32, i32, vp]
     _lib = L
     return L
 
@@ -417,6 +428,32 @@ def _fof_arrays(bodies, systems):
     {groups, largest} per system as an (systems, 2) int32 array -- nbx_fof_info_t's layout -- and the scalar passes."""
     return [np.zeros(max(bodies, 1), dtype=np.int32), np.zeros(max(bodies, 1), dtype=np.int32),
             np.zeros((max(systems, 1), 2), dtype=np.int32), np.zeros(1, dtype=np.int32)]
+
+
+def _tidal_arrays(shape, dtype):
+    """(the six result arrays of a *_tidal call by key, the void* t[6] that points at them)."""
+    out = {k: np.zeros(shape, dtype=dtype) for k in TIDAL_KEYS}
+    return out, (ctypes.c_void_p * 6)(*[out[k].ctypes.data for k in TIDAL_KEYS])
+
+
+def tidal_matrix(res):
+    """The symmetric (..., 3, 3) tidal tensors, in fp64, of a result of tidal() or tidal_bodies(): a dict of the six TIDAL_KEYS
+    arrays of one shape."""
+    c = [np.asarray(res[k], dtype=np.float64) for k in TIDAL_KEYS]
+    return np.stack([np.stack([c[0], c[1], c[2]], axis=-1), np.stack([c[1], c[3], c[4]], axis=-1),
+                     np.stack([c[2], c[4], c[5]], axis=-1)], axis=-2)
+
+
+def tidal_radius(res, gm):
+    """(gm / lambda_max)^(1/3), in fp64, lambda_max the largest eigenvalue of every tensor of `res` -- the strongest stretching
+    -- and gm = G M of the object whose tidal radius is asked for (a scalar or an array of the tensors' shape); inf where
+    lambda_max <= 0, i.e. where the field compresses along every axis.  The object's own softening is ignored."""
+    lam = np.linalg.eigvalsh(tidal_matrix(res))[..., -1]
+    gm = np.broadcast_to(np.asarray(gm, dtype=np.float64), lam.shape)
+    out = np.full(lam.shape, np.inf)
+    pos = lam > 0
+    out[pos] = np.cbrt(gm[pos] / lam[pos])
+    return out
 
 
 def _binaries_arrays(shape, dtype, bound):
@@ -717,6 +754,26 @@ class Context(_Handle, _Leapfrog, _Adaptive, _Tracers):
         _check(self._L.nbx_binaries(self._h, *[_ptr(out[k]) for k in BINARIES_KEYS]), "nbx_binaries")
         return out
 
+    def tidal(self, px, py, pz):
+        """nbx_tidal: the tidal tensor of the resident bodies at the m points (px, py, pz) -- every body counts, a point is not a
+        body -- as {"t_xx", "t_xy", "t_xz", "t_yy", "t_yz", "t_zz"}, arrays of m.  Synchronises."""
+        _need(self._L, "nbx_tidal")
+        p = [np.ascontiguousarray(a, dtype=self.dtype) for a in (px, py, pz)]
+        if p[0].ndim != 1 or any(a.shape != p[0].shape for a in p):
+            raise NbxError(NBX_ERR_ARG, "array", "expected three arrays of one shape (m,), got %r" % ([a.shape for a in p],))
+        m = p[0].shape[0]
+        out, t = _tidal_arrays(m, self.dtype)
+        _check(self._L.nbx_tidal(self._h, m, *[_ptr(a) for a in p], t), "nbx_tidal")
+        return out
+
+    def tidal_bodies(self):
+        """nbx_tidal_bodies: the tidal tensor at every body, the body's own term never formed, as the six TIDAL_KEYS arrays of n
+        (all n bodies, also for a sliced context).  Synchronises."""
+        _need(self._L, "nbx_tidal_bodies")
+        out, t = _tidal_arrays(self.n, self.dtype)
+        _check(self._L.nbx_tidal_bodies(self._h, t), "nbx_tidal_bodies")
+        return out
+
     def fof(self, radius):
         """nbx_fof: the friends-of-friends groups at linking length `radius`, as {"label": (n,) int32 -- the lowest index of the
         body's group --, "size": (n,) int32, "groups", "largest", "passes"} (all n bodies, also for a sliced context).
@@ -888,6 +945,21 @@ class _Batch(_Handle, _Leapfrog, _Adaptive, _Tracers):
         self._call("field", first, count, m, *[_ptr(a) for a in p], *[_ptr(out[k]) for k in FIELD_KEYS])
         return out
 
+    def tidal(self, px, py, pz, first=0, count=None):
+        """<prefix>_tidal: the tidal tensor of members [first, first + count) (default: all from `first`), each at its own m
+        points -- px, py, pz of shape (count, m), row k the points of member first + k -- as the six TIDAL_KEYS arrays
+        (count, m); for each member the bits Context.tidal() returns for a context of the member's size holding its state and
+        given the same points; one launch for all of them.  Synchronises."""
+        _need(self._L, self._prefix + "_tidal")
+        count = self.members - first if count is None else count
+        p = [np.ascontiguousarray(a, dtype=self.dtype) for a in (px, py, pz)]
+        if p[0].ndim != 2 or p[0].shape[0] != max(count, 0) or any(a.shape != p[0].shape for a in p):
+            raise NbxError(NBX_ERR_ARG, "array", "expected three arrays of shape (%d, m), got %r" % (max(count, 0), [a.shape for a in p]))
+        m = p[0].shape[1]
+        out, t = _tidal_arrays((max(count, 0), m), self.dtype)
+        self._call("tidal", first, count, m, *[_ptr(a) for a in p], t)
+        return out
+
     def _tracers_call(self, name, *args):
         _need(self._L, "%s_tracers_%s" % (self._prefix, name))
         self._call("tracers_" + name, *args)
@@ -962,6 +1034,16 @@ class Ensemble(_Batch):
         flat = _knn_arrays(rows, k, self.dtype)
         self._call("knn", first, count, k, *[_ptr(flat[key]) for key in KNN_KEYS])
         return {key: flat[key][:rows * k].reshape(max(count, 0), self.n, k) for key in KNN_KEYS}
+
+    def tidal_bodies(self, first=0, count=None):
+        """nbx_ensemble_tidal_bodies: the six TIDAL_KEYS arrays (count, n) of members [first, first + count) (default: all from
+        `first`) -- for each member the bits Context.tidal_bodies() returns for a context of n bodies holding its state; one
+        launch for all of them.  Synchronises."""
+        _need(self._L, "nbx_ensemble_tidal_bodies")
+        count = self.members - first if count is None else count
+        out, t = _tidal_arrays((max(count, 0), self.n), self.dtype)
+        self._call("tidal_bodies", first, count, t)
+        return out
 
     def binaries(self, bound=True, first=0, count=None):
         """nbx_ensemble_binaries: {"partner", "energy", "bound"}, arrays (count, n), of members [first, first + count) (default:
@@ -1068,6 +1150,17 @@ class Ragged(_Batch):
         self._call("knn", first, count, k, *[_ptr(flat[key]) for key in KNN_KEYS])
         at = np.concatenate([[0], np.cumsum(sizes)]).astype(int) * max(int(k), 0)
         return [{key: flat[key][at[m]:at[m + 1]].reshape(sizes[m], k).copy() for key in KNN_KEYS} for m in range(len(sizes))]
+
+    def tidal_bodies(self, first=0, count=None):
+        """nbx_ragged_tidal_bodies: the six TIDAL_KEYS arrays of members [first, first + count) (default: all from `first`), ONE
+        array per key with the members end to end (member first + k at sum(sizes[first:first + k])) -- for each member the bits
+        Context.tidal_bodies() returns for a context of its size holding its state; one launch for all of them.  Synchronises."""
+        _need(self._L, "nbx_ragged_tidal_bodies")
+        count = self.members - first if count is None else count
+        total = sum(self._range(first, count))
+        out, t = _tidal_arrays(max(total, 1), self.dtype)  # >= 1: an address is wanted, also for an empty range
+        self._call("tidal_bodies", first, count, t)
+        return {k: out[k][:total] for k in TIDAL_KEYS}
 
     def binaries(self, bound=True, first=0, count=None):
         """nbx_ragged_binaries: one {"partner", "energy", "bound"} per member of [first, first + count) (default: all from
