@@ -134,6 +134,14 @@ struct Object {
   void* tidal_out = nullptr;
   void* tidal_tab = nullptr;
   size_t tidal_pts_cap = 0, tidal_part_cap = 0, tidal_out_cap = 0;
+  // clumps under a caller-supplied label (nbx_clumps.hip): the uploaded labels, the partial records followed by the count rows
+  // and the result records followed by the members, allocated on first use and grown likewise (sizes in bytes); clump_tab: a
+  // ragged ensemble's {pos_off, vel_off, out_off, n} per member, built on first use
+  void* clump_lab = nullptr;
+  void* clump_part = nullptr;
+  void* clump_out = nullptr;
+  void* clump_tab = nullptr;
+  size_t clump_lab_cap = 0, clump_part_cap = 0, clump_out_cap = 0;
   // resident tracers (nbx_tracers.hip): tr_m per system (0: none), every system's {x, y, z, 0} position and velocity records
   // one system after the other, and the partial rows of the pair work ([systems][tr_rows][tr_m] records, buffers of their own:
   // not the field's scratch), allocated by the first upload and grown likewise (sizes in bytes); tr_have: per system, its
@@ -347,7 +355,7 @@ inline void batch_release(Object* o) {
                   (void*)o->ts_dev, o->field_pts, o->field_part, o->field_out, o->field_tab, o->nb_part, o->nb_out, o->nb_tab, o->pc_part,
                   o->pc_out, o->pc_tab, o->knn_part, o->knn_out, o->knn_tab, o->fof_rec, o->fof_part,
                   o->fof_work, o->fof_out, o->fof_tab, o->bin_part, o->bin_out, o->bin_tab, o->tidal_pts, o->tidal_part,
-                  o->tidal_out, o->tidal_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
+                  o->tidal_out, o->tidal_tab, o->clump_lab, o->clump_part, o->clump_out, o->clump_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
     if (p) (void)hipFree(p);
   if (o->own_stream) (void)hipStreamDestroy(o->stream);
 }

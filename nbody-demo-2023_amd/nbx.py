@@ -99,6 +99,9 @@ BINARIES_KEYS = ("partner", "energy", "bound")
 TIDAL_SYMBOLS = ("nbx_tidal", "nbx_ensemble_tidal", "nbx_ragged_tidal",
                  "nbx_tidal_bodies", "nbx_ensemble_tidal_bodies", "nbx_ragged_tidal_bodies")
 TIDAL_KEYS = ("t_xx", "t_xy", "t_xz", "t_yy", "t_yz", "t_zz")
+# the symbols of include/nbx_clumps.h (clumps under a caller-supplied label: members, mass, centre, velocity, potential, energy)
+CLUMPS_SYMBOLS = ("nbx_clumps", "nbx_ensemble_clumps", "nbx_ragged_clumps")
+CLUMPS_KEYS = ("members", "gm", "centre_x", "centre_y", "centre_z", "velocity_x", "velocity_y", "velocity_z", "phi", "energy")
 GRAV = float(np.float32(6.67259e-11))  # the library's G: (float)6.67259e-11f, widened
 
 
@@ -161,6 +164,12 @@ class Timescale(ctypes.Structure):
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+class ClumpsOut(ctypes.Structure):
+    """nbx_clumps_out_t (include/nbx_clumps.h): every pointer may be NULL."""
+    _fields_ = [("members", ctypes.c_void_p), ("gm", ctypes.c_void_p), ("centre", ctypes.c_void_p * 3), ("velocity", ctypes.c_void_p * 3),
+                ("phi", ctypes.c_void_p), ("energy", ctypes.c_void_p)]
 
 
 class EnsembleStats(ctypes.Structure):
@@ -330,6 +339,10 @@ def load():
         L.nbx_tidal_bodies.argtypes = [vp, vp]
         L.nbx_ensemble_tidal_bodies.argtypes = [vp, i32, i32, vp]
         L.nbx_ragged_tidal_bodies.argtypes = [vp, i32, i32, vp]
+    if hasattr(L, "nbx_clumps"):  # likewise for nbx_clumps.hip
+        L.nbx_clumps.argtypes = [vp, vp, ctypes.POINTER(ClumpsOut)]
+        L.nbx_ensemble_clumps.argtypes = [vp, i32, i32, vp, ctypes.POINTER(ClumpsOut)]
+        L.nbx_ragged_clumps.argtypes = [vp, i32, i32, vp, ctypes.POINTER(ClumpsOut)]
     _lib = L
     return L
 
@@ -494,6 +507,69 @@ def binary_catalogue(partner, energy, mass, x, y, z, vx, vy, vz):
     order = np.lexsort((i, -binding))
     return {"i": i[order], "j": j[order], "energy": e[order], "a": a[order], "ecc": ecc[order], "period": period[order],
             "binding": binding[order]}
+
+
+def _clumps_arrays(shape, dtype):
+    """(the ten result arrays of a *_clumps call by key, the nbx_clumps_out_t that points at them)."""
+    out = {k: np.zeros(shape, dtype=np.int32 if k == "members" else dtype) for k in CLUMPS_KEYS}
+    a = [out[k].ctypes.data for k in CLUMPS_KEYS]
+    return out, ClumpsOut(a[0], a[1], (ctypes.c_void_p * 3)(*a[2:5]), (ctypes.c_void_p * 3)(*a[5:8]), a[8], a[9])
+
+
+def _clumps_label(label, shape):
+    """The caller's labels as a contiguous int32 array of `shape` (at least one element: an address is wanted)."""
+    lab = np.asarray(label)
+    if lab.shape != shape or lab.dtype.kind not in "iu" or (lab.size and (lab.min() < -2 ** 31 or lab.max() > 2 ** 31 - 1)):
+        raise NbxError(NBX_ERR_ARG, "label", "expected integers that fit int32, of shape %r, got %s %r" % (shape, lab.dtype, lab.shape))
+    lab = np.ascontiguousarray(lab, dtype=np.int32).reshape(-1)
+    return lab if lab.size else np.zeros(1, dtype=np.int32)
+
+
+def clump_catalogue(label, result, mass, min_members=2):
+    """The clumps of one system from the labels given to clumps(), its result and the bodies' masses, in fp64: for every label
+    >= 0 with at least `min_members` bodies one row of {"label", "members": (g,) int64, "gm": (g,), "centre", "velocity": (g, 3)
+    -- the values the clump's first member returned; every member returns the same bits --, "kinetic": sum m_i |v_i - V|^2 / 2
+    in the clump's own frame (from energy - phi), "potential": sum m_i phi_i / 2, "virial": 2 kinetic / |potential| (inf where
+    the potential is 0), "bound": (g,) int64, the members with energy < 0}, ordered by (-members, label)."""
+    label = np.asarray(label, dtype=np.int64)
+    mass = np.asarray(mass, dtype=np.float64)
+    r = {k: np.asarray(result[k], dtype=np.int64 if k == "members" else np.float64) for k in CLUMPS_KEYS}
+    if label.ndim != 1 or mass.shape != label.shape or any(v.shape != label.shape for v in r.values()):
+        raise NbxError(NBX_ERR_ARG, "clump_catalogue", "expected label, mass and the ten arrays of a clumps() result of one shape (n,)")
+    at = np.nonzero(label >= 0)[0]
+    names, first, inverse, members = np.unique(label[at], return_index=True, return_inverse=True, return_counts=True)
+    g = len(names)
+    kinetic = np.bincount(inverse, weights=mass[at] * (r["energy"][at] - r["phi"][at]), minlength=g)
+    potential = 0.5 * np.bincount(inverse, weights=mass[at] * r["phi"][at], minlength=g)
+    bound = np.bincount(inverse, weights=(r["energy"][at] < 0.0).astype(np.float64), minlength=g).astype(np.int64)
+    keep = np.nonzero(members >= min_members)[0]
+    keep = keep[np.lexsort((names[keep], -members[keep]))]
+    lead = at[first[keep]] if g else np.zeros(0, dtype=np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        virial = np.where(potential[keep] != 0.0, 2.0 * kinetic[keep] / np.abs(potential[keep]), np.inf)
+    return {"label": names[keep].astype(np.int64), "members": members[keep].astype(np.int64), "gm": r["gm"][lead],
+            "centre": np.stack([r["centre_" + a][lead] for a in "xyz"], axis=1),
+            "velocity": np.stack([r["velocity_" + a][lead] for a in "xyz"], axis=1),
+            "kinetic": kinetic[keep], "potential": potential[keep], "virial": virial, "bound": bound[keep]}
+
+
+def unbind(obj, label, max_iter=32):
+    """The unbinding iteration on a Context or an Ensemble: obj.clumps(label), then label = -1 wherever energy >= 0 (a clump of
+    one body has energy 0 and leaves too), repeated until a call changes nothing or max_iter calls have been made.  Returns
+    (label, result, iterations): the final labels (int32, the shape given), the result of the last call and the number of calls.
+    Where the iteration ended by itself the result is that of the final labels."""
+    if not isinstance(obj, (Context, Ensemble)):
+        raise NbxError(NBX_ERR_ARG, "unbind", "expected a Context or an Ensemble")
+    label = np.array(label, dtype=np.int32)
+    result, iterations = None, 0
+    while iterations < max_iter:
+        result = obj.clumps(label)
+        iterations += 1
+        leave = (label >= 0) & (result["energy"] >= 0)
+        if not leave.any():
+            break
+        label[leave] = -1
+    return label, result, iterations
 
 
 def fof_catalogue(label, mass, x, y, z, min_members=2):
@@ -752,6 +828,17 @@ class Context(_Handle, _Leapfrog, _Adaptive, _Tracers):
         _need(self._L, "nbx_binaries")
         out = _binaries_arrays((self.n,), self.dtype, bound)
         _check(self._L.nbx_binaries(self._h, *[_ptr(out[k]) for k in BINARIES_KEYS]), "nbx_binaries")
+        return out
+
+    def clumps(self, label):
+        """nbx_clumps: under the int32 labels `label` (n,) -- any value >= 0 names a clump, a negative one means "in no clump" --
+        for every body the members, G m, centre and mean velocity of its clump, the potential of the clump's other members at
+        the body and its specific energy in the clump's frame, as the ten CLUMPS_KEYS arrays of n.  A sliced context is refused.
+        Synchronises."""
+        _need(self._L, "nbx_clumps")
+        lab = _clumps_label(label, (self.n,))
+        out, a = _clumps_arrays((self.n,), self.dtype)
+        _check(self._L.nbx_clumps(self._h, _ptr(lab), ctypes.byref(a)), "nbx_clumps")
         return out
 
     def tidal(self, px, py, pz):
@@ -1045,6 +1132,17 @@ class Ensemble(_Batch):
         self._call("tidal_bodies", first, count, t)
         return out
 
+    def clumps(self, label, first=0, count=None):
+        """nbx_ensemble_clumps: under the int32 labels `label` (count, n), member-local, the ten CLUMPS_KEYS arrays (count, n) of
+        members [first, first + count) (default: all from `first`) -- for each member the bits Context.clumps() returns for a
+        context of n bodies holding its state and labels; one launch for all of them.  Synchronises."""
+        _need(self._L, "nbx_ensemble_clumps")
+        count = self.members - first if count is None else count
+        lab = _clumps_label(label, (max(count, 0), self.n))
+        out, a = _clumps_arrays((max(count, 0), self.n), self.dtype)
+        self._call("clumps", first, count, _ptr(lab), ctypes.byref(a))
+        return out
+
     def binaries(self, bound=True, first=0, count=None):
         """nbx_ensemble_binaries: {"partner", "energy", "bound"}, arrays (count, n), of members [first, first + count) (default:
         all from `first`) -- for each member the bits Context.binaries() returns for a context of n bodies holding its state; one
@@ -1161,6 +1259,24 @@ class Ragged(_Batch):
         out, t = _tidal_arrays(max(total, 1), self.dtype)  # >= 1: an address is wanted, also for an empty range
         self._call("tidal_bodies", first, count, t)
         return {k: out[k][:total] for k in TIDAL_KEYS}
+
+    def clumps(self, label, first=0, count=None):
+        """nbx_ragged_clumps: under `label`, a list of one int32 array of sizes[k] per member of [first, first + count) (default:
+        all from `first`), member-local, one dict of the ten CLUMPS_KEYS arrays of sizes[k] per member -- the bits
+        Context.clumps() returns for a context of sizes[k] bodies holding that member's state and labels; one launch for all of
+        them.  Synchronises."""
+        _need(self._L, "nbx_ragged_clumps")
+        count = self.members - first if count is None else count
+        sizes = self._range(first, count)
+        label = [np.asarray(l) for l in label]
+        if sizes and [l.shape for l in label] != [(n,) for n in sizes]:
+            raise NbxError(NBX_ERR_ARG, "label", "expected one array of sizes[k] labels per member of the range")
+        total = sum(sizes)
+        lab = _clumps_label(np.concatenate(label) if sizes else np.zeros(0, dtype=np.int32), (total,))
+        flat, a = _clumps_arrays((max(total, 1),), self.dtype)  # >= 1: an address is wanted, also for an empty range
+        self._call("clumps", first, count, _ptr(lab), ctypes.byref(a))
+        at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+        return [{k: flat[k][at[m]:at[m + 1]].copy() for k in CLUMPS_KEYS} for m in range(len(sizes))]
 
     def binaries(self, bound=True, first=0, count=None):
         """nbx_ragged_binaries: one {"partner", "energy", "bound"} per member of [first, first + count) (default: all from
