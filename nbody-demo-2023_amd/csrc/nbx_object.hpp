@@ -142,6 +142,15 @@ struct Object {
   void* clump_out = nullptr;
   void* clump_tab = nullptr;
   size_t clump_lab_cap = 0, clump_part_cap = 0, clump_out_cap = 0;
+  // neighbour lists (nbx_nlist.hip): the (split, body) segments, the scan's arrays (within, offsets, block sums) and the two
+  // lists, the lists sized by a call's total and never by the caller's capacity, allocated on first use and grown likewise
+  // (sizes in bytes); nl_tab: a ragged ensemble's {pos_off, out_off, n} per member, built on first use
+  void* nl_seg = nullptr;
+  void* nl_scan = nullptr;
+  void* nl_index = nullptr;
+  void* nl_r2 = nullptr;
+  void* nl_tab = nullptr;
+  size_t nl_seg_cap = 0, nl_scan_cap = 0, nl_index_cap = 0, nl_r2_cap = 0;
   // resident tracers (nbx_tracers.hip): tr_m per system (0: none), every system's {x, y, z, 0} position and velocity records
   // one system after the other, and the partial rows of the pair work ([systems][tr_rows][tr_m] records, buffers of their own:
   // not the field's scratch), allocated by the first upload and grown likewise (sizes in bytes); tr_have: per system, its
@@ -355,7 +364,8 @@ inline void batch_release(Object* o) {
                   (void*)o->ts_dev, o->field_pts, o->field_part, o->field_out, o->field_tab, o->nb_part, o->nb_out, o->nb_tab, o->pc_part,
                   o->pc_out, o->pc_tab, o->knn_part, o->knn_out, o->knn_tab, o->fof_rec, o->fof_part,
                   o->fof_work, o->fof_out, o->fof_tab, o->bin_part, o->bin_out, o->bin_tab, o->tidal_pts, o->tidal_part,
-                  o->tidal_out, o->tidal_tab, o->clump_lab, o->clump_part, o->clump_out, o->clump_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
+                  o->tidal_out, o->tidal_tab, o->clump_lab, o->clump_part, o->clump_out, o->clump_tab, o->nl_seg, o->nl_scan, o->nl_index,
+                  o->nl_r2, o->nl_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
     if (p) (void)hipFree(p);
   if (o->own_stream) (void)hipStreamDestroy(o->stream);
 }

@@ -102,6 +102,11 @@ TIDAL_KEYS = ("t_xx", "t_xy", "t_xz", "t_yy", "t_yz", "t_zz")
 # the symbols of include/nbx_clumps.h (clumps under a caller-supplied label: members, mass, centre, velocity, potential, energy)
 CLUMPS_SYMBOLS = ("nbx_clumps", "nbx_ensemble_clumps", "nbx_ragged_clumps")
 CLUMPS_KEYS = ("members", "gm", "centre_x", "centre_y", "centre_z", "velocity_x", "velocity_y", "velocity_z", "phi", "energy")
+# the symbols of include/nbx_nlist.h (every body's neighbours within a radius, as a list), kept apart likewise
+NLIST_SYMBOLS = ("nbx_nlist", "nbx_ensemble_nlist", "nbx_ragged_nlist")
+NLIST_KEYS = ("offsets", "index", "r2", "total")
+NLIST_MAX_CAPACITY = 1 << 28  # entries per call
+NLIST_FIRST_GUESS = 16        # entries per body nlist() tries before it asks again with the exact total
 GRAV = float(np.float32(6.67259e-11))  # the library's G: (float)6.67259e-11f, widened
 
 
@@ -343,6 +348,11 @@ def load():
         L.nbx_clumps.argtypes = [vp, vp, ctypes.POINTER(ClumpsOut)]
         L.nbx_ensemble_clumps.argtypes = [vp, i32, i32, vp, ctypes.POINTER(ClumpsOut)]
         L.nbx_ragged_clumps.argtypes = [vp, i32, i32, vp, ctypes.POINTER(ClumpsOut)]
+    if hasattr(L, "nbx_nlist"):  # likewise for nbx_nlist.hip
+        i64 = ctypes.c_int64
+        L.nbx_nlist.argtypes = [vp, dbl, i64, vp, vp, vp, vp]
+        L.nbx_ensemble_nlist.argtypes = [vp, i32, i32, dbl, i64, vp, vp, vp, vp]
+        L.nbx_ragged_nlist.argtypes = [vp, i32, i32, dbl, i64, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -441,6 +451,55 @@ def _fof_arrays(bodies, systems):
     {groups, largest} per system as an (systems, 2) int32 array -- nbx_fof_info_t's layout -- and the scalar passes."""
     return [np.zeros(max(bodies, 1), dtype=np.int32), np.zeros(max(bodies, 1), dtype=np.int32),
             np.zeros((max(systems, 1), 2), dtype=np.int32), np.zeros(1, dtype=np.int32)]
+
+
+def _nlist(call, bodies, dtype, radius, capacity):
+    """The two-call protocol of a *_nlist entry point: call(radius, capacity, offsets, index, r2, total) raises on a status other
+    than NBX_OK.  capacity None: NLIST_FIRST_GUESS entries per body first, then the exact total if that was too small.  An explicit
+    capacity is one call; where the lists do not fit it, "index" and "r2" are None and "total" says what they need."""
+    offsets = np.zeros(max(bodies, 0) + 1, dtype=np.int64)
+    total = np.zeros(1, dtype=np.int64)
+    tries = [min(NLIST_FIRST_GUESS * max(bodies, 0), NLIST_MAX_CAPACITY), None] if capacity is None else [int(capacity)]
+    for cap in tries:
+        cap = int(total[0]) if cap is None else cap
+        index = np.zeros(max(cap, 1), dtype=np.int32)  # at least one element each: _ptr wants an address
+        r2 = np.zeros(max(cap, 1), dtype=dtype)
+        call(radius, cap, _ptr(offsets), _ptr(index) if cap > 0 else None, _ptr(r2) if cap > 0 else None, _ptr(total))
+        t = int(total[0])
+        if t <= cap:
+            return {"offsets": offsets, "index": index[:t].copy() if 2 * t < index.size else index[:t],
+                    "r2": r2[:t].copy() if 2 * t < r2.size else r2[:t], "total": t}
+    return {"offsets": offsets, "index": None, "r2": None, "total": int(total[0])}
+
+
+def nlist_pairs(nl, n=None):
+    """The unique pairs of an nlist() result: (pairs, r2), pairs a (k, 2) int64 array of (i, j), i < j, in the lists' order (by i,
+    then by j), r2 their softened squared distances.  Every pair is in two lists with the same r2 bits; this keeps the one in
+    the lower body's.  n None: the result of a Context.  n an int: of an Ensemble of n bodies per member; n a sequence of sizes:
+    of a Ragged range of those members -- then one (pairs, r2) per member, i and j member-local."""
+    offsets = np.asarray(nl["offsets"], dtype=np.int64)
+    if nl["index"] is None or nl["r2"] is None:
+        raise NbxError(NBX_ERR_ARG, "nlist_pairs", "the lists of this result were not filled (total exceeds the capacity)")
+    bodies = offsets.shape[0] - 1
+    if n is None:
+        sizes = [bodies]
+    elif np.ndim(n) == 0:
+        if int(n) <= 0 or bodies % int(n):
+            raise NbxError(NBX_ERR_ARG, "nlist_pairs", "the result's bodies are no multiple of n")
+        sizes = [int(n)] * (bodies // int(n))
+    else:
+        sizes = [int(v) for v in n]
+        if sum(sizes) != bodies:
+            raise NbxError(NBX_ERR_ARG, "nlist_pairs", "the sizes do not add up to the result's bodies")
+    at = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    out = []
+    for m, size in enumerate(sizes):
+        lo, hi = int(offsets[at[m]]), int(offsets[at[m + 1]])
+        i = np.repeat(np.arange(size, dtype=np.int64), np.diff(offsets[at[m]:at[m + 1] + 1]))
+        j = np.asarray(nl["index"][lo:hi], dtype=np.int64)
+        keep = i < j
+        out.append((np.stack([i[keep], j[keep]], axis=1).reshape(-1, 2), np.asarray(nl["r2"][lo:hi])[keep]))
+    return out[0] if n is None else out
 
 
 def _tidal_arrays(shape, dtype):
@@ -870,6 +929,14 @@ class Context(_Handle, _Leapfrog, _Adaptive, _Tracers):
         _check(self._L.nbx_fof(self._h, radius, _ptr(label), _ptr(size), _ptr(info), _ptr(passes)), "nbx_fof")
         return {"label": label[:self.n], "size": size[:self.n], "groups": int(info[0, 0]), "largest": int(info[0, 1]), "passes": int(passes[0])}
 
+    def nlist(self, radius, capacity=None):
+        """nbx_nlist: for every body the indices of all bodies within `radius` (r2 <= h2 = fma(r, r, eps^2)), ascending, and their
+        r2, as {"offsets": (n + 1,) int64, "index": (total,) int32, "r2": (total,), "total"}: the list of body i is
+        index[offsets[i]:offsets[i + 1]].  capacity None: two calls at most; an int: one call, index and r2 None where
+        total exceeds it; 0: the counting call.  Synchronises once per pass."""
+        _need(self._L, "nbx_nlist")
+        return _nlist(lambda *a: _check(self._L.nbx_nlist(self._h, *a), "nbx_nlist"), self.n, self.dtype, radius, capacity)
+
     def paircount(self, radii):
         """nbx_paircount: the number of pairs i < j with r2(i, j) <= h2 for each of `radii` (any order, at most 256), a
         np.uint64 array of len(radii) -- of all n bodies, also for a sliced context; one pass over the pairs per 16 radii.
@@ -1166,6 +1233,15 @@ class Ensemble(_Batch):
         return {"label": label[:S * self.n].reshape(S, self.n), "size": size[:S * self.n].reshape(S, self.n), "groups": info[:S, 0].copy(),
                 "largest": info[:S, 1].copy(), "passes": int(passes[0])}
 
+    def nlist(self, radius, capacity=None, first=0, count=None):
+        """nbx_ensemble_nlist: what Context.nlist() returns, for members [first, first + count) (default: all from `first`) in one
+        result: offsets (count * n + 1,) run across the members, body i of member first + k is at k * n + i, the indices are
+        member-local -- for each member the bits Context.nlist() returns for a context of n bodies holding its state.
+        nbx.nlist_pairs(result, n) splits it by member."""
+        _need(self._L, "nbx_ensemble_nlist")
+        count = self.members - first if count is None else count
+        return _nlist(lambda *a: self._call("nlist", first, count, *a), max(count, 0) * self.n, self.dtype, radius, capacity)
+
     def paircount(self, radii, first=0, count=None):
         """nbx_ensemble_paircount: a np.uint64 array (count, len(radii)) of members [first, first + count) (default: all from
         `first`) -- for each member the bits Context.paircount() returns for a context of n bodies holding its state; one launch
@@ -1303,6 +1379,15 @@ class Ragged(_Batch):
         at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
         return [{"label": label[at[m]:at[m + 1]].copy(), "size": size[at[m]:at[m + 1]].copy(), "groups": int(info[m, 0]),
                  "largest": int(info[m, 1]), "passes": int(passes[0])} for m in range(len(sizes))]
+
+    def nlist(self, radius, capacity=None, first=0, count=None):
+        """nbx_ragged_nlist: what Context.nlist() returns, for members [first, first + count) (default: all from `first`) in one
+        result: the members' bodies end to end, offsets run across them, the indices are member-local -- for each member the
+        bits Context.nlist() returns for a context of sizes[k] bodies holding its state.  nbx.nlist_pairs(result, sizes of the
+        range) splits it by member."""
+        _need(self._L, "nbx_ragged_nlist")
+        count = self.members - first if count is None else count
+        return _nlist(lambda *a: self._call("nlist", first, count, *a), sum(self._range(first, count)), self.dtype, radius, capacity)
 
     def paircount(self, radii, first=0, count=None):
         """nbx_ragged_paircount: a np.uint64 array (count, len(radii)) of members [first, first + count) (default: all from
