@@ -15,7 +15,11 @@ reciprocal square root seed within 2^-24, 55.5 u to first order.  window(pair) =
 
 restate() walks the pairs the way the kernels do -- j splits of field_shape(n, n), a candidate per split, the splits combined in
 ascending order on strict < -- so that the faults a kernel of this structure can have may be planted (FAULTS); without a fault
-the structure does not show in the result.
+the structure does not show in the result.  VELOCITY_FAULTS are the ways of pairing the second staged tile, the velocity records,
+with the wrong position record; they show only where the velocities differ from record to record (lattice_ref.hubble).
+
+binaries(), ambiguity(), restate() and compare() take rows=: only those bodies, each against ALL j, O(rows n) -- the reference
+of the cloud of 35 937 bodies of tests/test_large_shapes_gpu.py.
 
 The demo's own initial conditions have G m of about 1e-11: nothing there is bound.  The states here have masses of order 1/G.
 """
@@ -41,9 +45,18 @@ LATTICE_K = NB.LATTICE_K
 FAULTS = ("self not masked", "padding record not masked", "padding velocity read", "ties to the highest j",
           "finish takes a later split on ties", "a split row dropped", "<= instead of < in the count", "m_j alone instead of m_i + m_j",
           "indices offset by the member's place")
+# what a kernel that stages a SECOND tile, the velocity records of the same j, can get wrong in pairing the two; kept apart from
+# FAULTS: on a state at rest every one of them changes nothing (tests/test_large_shapes_cpu.py shows it), which is why the large
+# shapes carry velocities that are a function of the position (lattice_ref.hubble)
+VELOCITY_FAULTS = ("velocity of record j + 1 read for record j", "velocity tile of the first split read in every split",
+                   "velocity offset of the member not applied", "velocity index wraps at 65 536")
+VELOCITY_WRAP = 65536
 # seed of cloud(n) and of clustered(n): the first, counting up from 100 + n % 97 and 300 + n % 97, whose state has no ambiguous
 # body in either precision
 CLOUD_SEEDS = {1: 101, 2: 102, 255: 161, 256: 162, 257: 163, 513: 128, 1025: 155, 2049: 112, 4097: 123}
+# cloud(35937), the large shapes' (tests/test_large_shapes_gpu.py): the first, counting up from 100 + n % 97, whose SAMPLED rows
+# (test_large_shapes_gpu.cloud_rows) hold no ambiguous body in either precision and no body bound to nobody or to everybody
+CLOUD_SEEDS[35937] = 147
 CLUSTERED_SEEDS = {513: 328, 2049: 312}
 SPEED = 1.4  # a component of a cloud velocity is uniform in [-SPEED, SPEED]: |dv|^2 / 2 is about 2, what G (m_i + m_j) / r is at r = 1
 
@@ -148,40 +161,49 @@ def _arrays(state):
     return x, v, gm_as_uploaded(state["mass"])
 
 
-def _terms(x, v, gm, lo, hi, xj=None, vj=None, gmj=None, alone=False):
-    """(A, B) of rows lo .. hi against all records j (default: the bodies themselves)."""
+def _terms(x, v, gm, i, xj=None, vj=None, gmj=None, alone=False):
+    """(A, B) of the bodies i (an index array) against all records j (default: the bodies themselves)."""
     xj, vj, gmj = x if xj is None else xj, v if vj is None else vj, gm if gmj is None else gmj
-    d = [xj[c][None, :] - x[c][lo:hi, None] for c in range(3)]
+    d = [xj[c][None, :] - x[c][i, None] for c in range(3)]
     r2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + EPS2
-    w = [vj[c][None, :] - v[c][lo:hi, None] for c in range(3)]
+    w = [vj[c][None, :] - v[c][i, None] for c in range(3)]
     a = 0.5 * (w[0] * w[0] + w[1] * w[1] + w[2] * w[2])
-    s = gmj[None, :] + (0.0 if alone else gm[lo:hi, None])
+    s = gmj[None, :] + (0.0 if alone else gm[i, None])
     return a, s / np.sqrt(r2)
 
 
-def binaries(state, precision, chunk=512):
+def _row_chunks(n, rows, chunk):
+    """The bodies asked for -- all n, or `rows` -- in chunks: (where the chunk's values go, the bodies)."""
+    rows = np.arange(n) if rows is None else np.asarray(rows, dtype=np.int64)
+    assert rows.ndim == 1 and (rows.size == 0 or (0 <= rows.min() and rows.max() < n))
+    return rows, [(slice(lo, min(len(rows), lo + chunk)), rows[lo:lo + chunk]) for lo in range(0, len(rows), chunk)]
+
+
+def binaries(state, precision, chunk=512, rows=None):
     """{"partner", "energy", "bound"} of the state as stored -- the plain argmin (numpy's takes the first, i.e. lowest, index of
     equal values) and the plain count, in row chunks -- and what the comparison needs: "mag", A + B of the winning pair, and
-    "bound_lo", "bound_hi", the bracket of the count."""
+    "bound_lo", "bound_hi", the bracket of the count.  rows: only these bodies, each against ALL j -- O(rows n); entry k of every
+    array is body rows[k]'s."""
     x, v, gm = _arrays(state)
     n = len(gm)
     g = GATE[precision] * U[precision]
-    out = {"partner": np.full(n, -1, dtype=np.int32), "energy": np.full(n, np.inf), "bound": np.zeros(n, dtype=np.int32),
-           "mag": np.zeros(n), "bound_lo": np.zeros(n, dtype=np.int32), "bound_hi": np.zeros(n, dtype=np.int32)}
-    for lo in range(0, n, chunk):
-        hi = min(n, lo + chunk)
-        a, b = _terms(x, v, gm, lo, hi)
+    rows, chunks = _row_chunks(n, rows, chunk)
+    r = len(rows)
+    out = {"partner": np.full(r, -1, dtype=np.int32), "energy": np.full(r, np.inf), "bound": np.zeros(r, dtype=np.int32),
+           "mag": np.zeros(r), "bound_lo": np.zeros(r, dtype=np.int32), "bound_hi": np.zeros(r, dtype=np.int32)}
+    for at, i in chunks:
+        a, b = _terms(x, v, gm, i)
         e, win = a - b, g * (a + b)
-        own = (np.arange(hi - lo), np.arange(lo, hi))
+        own = (np.arange(len(i)), i)
         e[own] = np.inf
-        out["bound"][lo:hi] = (e < 0).sum(axis=1)
-        out["bound_lo"][lo:hi] = (e + win < 0).sum(axis=1)
-        out["bound_hi"][lo:hi] = (e - win < 0).sum(axis=1)
+        out["bound"][at] = (e < 0).sum(axis=1)
+        out["bound_lo"][at] = (e + win < 0).sum(axis=1)
+        out["bound_hi"][at] = (e - win < 0).sum(axis=1)
         if n > 1:
             j = e.argmin(axis=1)
-            out["partner"][lo:hi] = j
-            out["energy"][lo:hi] = e[own[0], j]
-            out["mag"][lo:hi] = (a + b)[own[0], j]
+            out["partner"][at] = j
+            out["energy"][at] = e[own[0], j]
+            out["mag"][at] = (a + b)[own[0], j]
     return out
 
 
@@ -195,34 +217,48 @@ def pair_energy(state, i, j):
     return a - b, a + b
 
 
-def ambiguity(state, precision, chunk=512):
-    """The number of bodies whose partner is ambiguous in the sense of the module's docstring."""
+def ambiguity(state, precision, chunk=512, rows=None):
+    """The number of bodies (of `rows`, where given) whose partner is ambiguous in the sense of the module's docstring."""
     x, v, gm = _arrays(state)
     n = len(gm)
     if n < 3:
         return 0
     g = GATE[precision] * U[precision]
     bad = 0
-    for lo in range(0, n, chunk):
-        hi = min(n, lo + chunk)
-        a, b = _terms(x, v, gm, lo, hi)
+    for _, i in _row_chunks(n, rows, chunk)[1]:
+        a, b = _terms(x, v, gm, i)
         e, win = a - b, g * (a + b)
-        rows = np.arange(hi - lo)
-        e[rows, np.arange(lo, hi)] = np.inf
+        k = np.arange(len(i))
+        e[k, i] = np.inf
         j = e.argmin(axis=1)
-        top = e[rows, j] + win[rows, j]
+        top = e[k, j] + win[k, j]
         low = e - win
-        low[rows, j] = np.inf
+        low[k, j] = np.inf
         bad += int((low.min(axis=1) <= top).sum())
     return bad
 
 
-def restate(state, precision, fault=None, offset=0, chunk=512):
+def velocity_map(n_rec, per, fault):
+    """Which velocity record a kernel with `fault` pairs with position record j, j < n_rec (-1: a zero record), per = the
+    tiles of a split.  None: no velocity fault, record j."""
+    j = np.arange(n_rec)
+    if fault == "velocity of record j + 1 read for record j":
+        return np.where(j + 1 < n_rec, j + 1, -1)
+    if fault == "velocity tile of the first split read in every split":
+        return j % (per * TILE)
+    if fault == "velocity index wraps at 65 536":
+        return j % VELOCITY_WRAP
+    return None
+
+
+def restate(state, precision, fault=None, offset=0, chunk=512, rows=None, member0=None):
     """The same values by the kernels' structure: the j range in splits of field_shape(n, n) over the padded records (zero
     position, zero mass; the velocity buffer has NO padding: what lies behind n is somebody else's), per split the lowest j of
     the smallest e (strict <, j ascending) and the count, the splits combined in ascending order on strict <.  `fault`: one of
-    FAULTS, planted; `offset`: the member's place, for the fault that adds it."""
-    assert fault is None or fault in FAULTS, fault
+    FAULTS or VELOCITY_FAULTS, planted; `offset`: the member's place, for the fault that adds it; `member0`: the state of the
+    batch object's first member, whose velocity records a kernel that does not apply the member's velocity offset reads (behind
+    its last one: the next member's, i.e. this state's own); `rows`: as binaries()."""
+    assert fault is None or fault in FAULTS + VELOCITY_FAULTS, fault
     x, v, gm = _arrays(state)
     n = len(gm)
     _, tiles, splits, per = field_shape(n, n)
@@ -232,21 +268,28 @@ def restate(state, precision, fault=None, offset=0, chunk=512):
     gmp = np.concatenate([gm, pad])
     behind = [np.resize(c[::-1], n_rec - n) for c in v]  # what a read behind the last velocity finds: other bodies' velocities
     vp = [np.concatenate([c, b if fault == "padding velocity read" else pad]) for c, b in zip(v, behind)]
-    out = {"partner": np.full(n, -1, dtype=np.int32), "energy": np.full(n, np.inf), "bound": np.zeros(n, dtype=np.int32)}
+    if fault == "velocity offset of the member not applied":
+        v0 = [np.asarray(member0[k], dtype=np.float64) for k in VEL]
+        vp = [np.resize(np.concatenate([c0, c]), n_rec) for c0, c in zip(v0, v)]  # the j side alone: the i side is the column's own read
+    vmap = velocity_map(n_rec, per, fault)
+    if vmap is not None:
+        vp = [np.where(vmap >= 0, c[np.maximum(vmap, 0)], 0.0) for c in vp]
+    rows_all, chunks = _row_chunks(n, rows, chunk)
+    r = len(rows_all)
+    out = {"partner": np.full(r, -1, dtype=np.int32), "energy": np.full(r, np.inf), "bound": np.zeros(r, dtype=np.int32)}
     jj = np.arange(n_rec)
-    for lo in range(0, n, chunk):
-        hi = min(n, lo + chunk)
-        a, b = _terms(x, v, gm, lo, hi, xp, vp, gmp, alone=fault == "m_j alone instead of m_i + m_j")
+    for at, i in chunks:
+        a, b = _terms(x, v, gm, i, xp, vp, gmp, alone=fault == "m_j alone instead of m_i + m_j")
         e = a - b
-        rows = np.arange(hi - lo)
+        rows = np.arange(len(i))
         ok = np.ones(e.shape, dtype=bool)
         if fault != "self not masked":
-            ok[rows, np.arange(lo, hi)] = False
+            ok[rows, i] = False
         ok[:, n:] = fault in ("padding record not masked", "padding velocity read")
         neg = (e <= 0) if fault == "<= instead of < in the count" else (e < 0)
-        best = np.full(hi - lo, np.inf)
-        bj = np.full(hi - lo, -1, dtype=np.int64)
-        cnt = np.zeros(hi - lo, dtype=np.int64)
+        best = np.full(len(i), np.inf)
+        bj = np.full(len(i), -1, dtype=np.int64)
+        cnt = np.zeros(len(i), dtype=np.int64)
         for s in range(splits):
             if fault == "a split row dropped" and s == splits - 1 and splits > 1:
                 continue
@@ -263,16 +306,22 @@ def restate(state, precision, fault=None, offset=0, chunk=512):
             cnt += (neg[:, j0:j1] & ok[:, j0:j1]).sum(axis=1)
         if fault == "indices offset by the member's place":
             bj = np.where(bj >= 0, bj + offset, bj)
-        out["partner"][lo:hi], out["energy"][lo:hi], out["bound"][lo:hi] = bj, best, cnt
+        out["partner"][at], out["energy"][at], out["bound"][at] = bj, best, cnt
     return out
 
 
-def compare(got, want, state, precision, bound=True):
+def compare(got, want, state, precision, bound=True, rows=None):
     """What the device tests ask of a result `got` against the reference `want` = binaries(state): (problems, the largest energy
     error in units of u (A + B)).  partner equal on every body; energy within the gate of the reference value of ITS OWN pair
-    and of the reference minimum; bound inside the bracket."""
+    and of the reference minimum; bound inside the bracket.  rows: `want` = binaries(state, rows=rows) and `got`, a result over
+    all bodies, is held to it on those bodies alone."""
     problems = []
     n = len(want["partner"])
+    total = len(state["mass"])
+    body = np.arange(total) if rows is None else np.asarray(rows, dtype=np.int64)
+    if rows is not None:
+        full = all(np.asarray(got[k]).shape == (total,) for k in (KEYS if bound else KEYS[:2]))
+        got = {k: np.asarray(got[k])[body] if full else np.zeros(0) for k in (KEYS if bound else KEYS[:2])}
     gp = np.asarray(got["partner"])
     if gp.shape != (n,) or not np.array_equal(gp, want["partner"]):
         problems.append("partner differs on %d bodies" % ((gp != want["partner"]).sum() if gp.shape == (n,) else n))
@@ -286,9 +335,9 @@ def compare(got, want, state, precision, bound=True):
         err_min = np.abs(ge[fin] - want["energy"][fin]) / (u * want["mag"][fin])
         worst = float(err_min.max())
         idx = np.nonzero(fin)[0]
-        valid = (gp.shape == (n,)) and ((gp[idx] >= 0) & (gp[idx] < n) & (gp[idx] != idx)).all()
+        valid = (gp.shape == (n,)) and ((gp[idx] >= 0) & (gp[idx] < total) & (gp[idx] != body[idx])).all()
         if valid:
-            e_own, mag_own = pair_energy(state, idx, gp[idx])
+            e_own, mag_own = pair_energy(state, body[idx], gp[idx])
             worst = max(worst, float((np.abs(ge[fin] - e_own) / (u * mag_own)).max()))
         if not valid or worst > GATE[precision]:
             problems.append("energy is %.1f u (A + B) from the reference" % worst)

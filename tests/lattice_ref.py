@@ -11,13 +11,20 @@ The planted lattice of the timescale checks is the lattice at rest with one body
 it has one, else -x: the coordinate stays a multiple of 1/16), given PLANT_SPEED in y and PLANT_MASS times the common mass: the
 extreme pair of all three values involves that body, so they follow from the 2 (n - 1) ordered pairs it is part of, O(n), and
 the closed-form background.
+
+The lattice in Hubble flow (hubble: v = H x, every mass 1 / G) gives the velocity-reading kernels, nbx_timescale and
+nbx_binaries, closed forms in which EVERY velocity record counts: hubble_timescale_expected in O(1), hubble_binaries_expected in
+O(offsets n).  restate_timescale restates the two-tile structure of nbx_timescale's kernels so that the pairing faults of
+binaries_ref.VELOCITY_FAULTS may be planted in it.
 """
 from decimal import Decimal, localcontext
 
 import numpy as np
 
+import binaries_ref as BR
 import neighbours_ref as NB
-from energy_ref import EPS2, gm_as_uploaded
+from energy_ref import EPS2, G32, gm_as_uploaded
+from potential_ref import diag_shape
 from timescale_ref import PLANT_MASS, PLANT_SPEED
 
 POS = NB.POS
@@ -100,6 +107,121 @@ def plant(rest, planted):
     s["vel_y"][planted] = T(PLANT_SPEED)
     s["mass"][planted] = T(PLANT_MASS)
     return s
+
+
+# ---- the lattice in Hubble flow ------------------------------------------------------------------------------------------------------
+# Every body of the lattice moves at v = H x, H a power of two, and has the mass 1 / G: every velocity is exact in both
+# precisions, v_j - v_i = H (x_j - x_i) exactly, and every pair quantity is a function of the squared lattice radius
+# s = 64 |x_j - x_i|^2 alone.  A velocity read from another record than the position's breaks that: the pair's |dv|^2 is then
+# H^2 |x_j' - x_i|^2, and whenever j' lies farther from i than j the approach rate exceeds H^2, the supremum of every true pair,
+# and the pair's energy changes sign, which the exact integer `bound` of body i shows.  A lattice at rest shows none of it.
+HUBBLE_H = (16.0, 8.0)  # the values the device tests use
+HUBBLE_MASS = 1.0 / float(G32)
+
+
+def hubble(k, precision, perm=False, H=16.0):
+    """neighbours_ref.lattice(k, precision, perm) with v = H x and every mass 1 / G, rounded to T."""
+    assert H > 0 and np.log2(H) == np.rint(np.log2(H))
+    s = NB.lattice(k, precision, perm)
+    T = NB.DTYPE[precision]
+    for p, w in zip(POS, VEL):
+        s[w] = np.ascontiguousarray((s[p].astype(np.float64) * H).astype(T))
+        assert np.array_equal(s[w].astype(np.float64), s[p].astype(np.float64) * H)  # exact
+    s["mass"] = np.full(k ** 3, HUBBLE_MASS, dtype=T)
+    return s
+
+
+def hubble_gm(precision):
+    """G m of a body of hubble(.), as uploaded: 1 to a rounding."""
+    return float(gm_as_uploaded(np.full(1, HUBBLE_MASS, dtype=NB.DTYPE[precision]))[0])
+
+
+def hubble_timescale_expected(k, H, precision):
+    """{approach_rate2, freefall_rate2, min_r2} of hubble(k, precision, ., H), in fp64, O(1): |dv|^2 / r2 = H^2 D^2 / (D^2 + eps^2)
+    grows with the distance D, so the corner-to-corner pair holds it; the other two are the face pairs', timescale_background's
+    with the Hubble lattice's G m."""
+    d2 = 3.0 * ((k - 1) / 8.0) ** 2
+    return {"approach_rate2": H * H * d2 / (d2 + EPS2), "freefall_rate2": 2.0 * hubble_gm(precision) / (FACE_R2 * np.sqrt(FACE_R2)),
+            "min_r2": FACE_R2}
+
+
+def hubble_energy(s, H, precision):
+    """(e, A + B) in fp64 of a pair at squared lattice radius s (an array or a number): A = H^2 s / 128, B = 2 G m / sqrt(s / 64 +
+    eps^2).  A grows and B falls with s: e is strictly increasing."""
+    s = np.asarray(s, dtype=np.float64)
+    a = 0.5 * H * H * s / 64.0
+    b = 2.0 * hubble_gm(precision) / np.sqrt(s / 64.0 + EPS2)
+    return a - b, a + b
+
+
+def hubble_shell(k, H, precision):
+    """(s_max, margin): the pairs of squared lattice radius <= s_max are the bound ones (e < 0), and margin is the smallest
+    |e| / (A + B) over all radii a k^3 lattice has -- how far the nearest shell stays from e = 0."""
+    s = np.arange(1, 3 * (k - 1) ** 2 + 1)
+    e, mag = hubble_energy(s, H, precision)
+    assert (np.diff(e) > 0).all()
+    return int((e < 0).sum()), float((np.abs(e) / mag).min())
+
+
+def hubble_binaries_expected(k, H, precision, perm=False):
+    """{"partner", "bound", "energy", "mag"} of hubble(k, precision, perm, H) from the geometry: e grows with the distance, so
+    the most bound partner is the lowest-numbered face neighbour (neighbours_ref.lattice_expected) and energy is e(1), one
+    value, with mag its A + B; bound[i] is the number of lattice sites within squared radius s_max of body i's, summed over the
+    integer offsets of that ball -- O(offsets n)."""
+    n = k ** 3
+    s_max, _ = hubble_shell(k, H, precision)
+    site = NB.lattice_order(k, perm)
+    c = (site // (k * k), (site // k) % k, site % k)
+    reach = int(np.floor(np.sqrt(s_max)))
+    bound = np.zeros(n, dtype=np.int64)
+    for a in range(-reach, reach + 1):
+        for b in range(-reach, reach + 1):
+            for d in range(-reach, reach + 1):
+                if 0 < a * a + b * b + d * d <= s_max:
+                    ok = np.ones(n, dtype=bool)
+                    for x, o in zip(c, (a, b, d)):
+                        ok &= (x + o >= 0) & (x + o < k)
+                    bound += ok
+    e, mag = hubble_energy(1.0, H, precision)
+    return {"partner": NB.lattice_expected(k, perm)[0], "bound": bound.astype(np.int32), "energy": float(e), "mag": float(mag)}
+
+
+TS_VELOCITY_FAULTS = BR.VELOCITY_FAULTS
+
+
+def restate_timescale(state, fault=None, member0=None, rows=None, chunk=256):
+    """nbx_timescale's three values by the structure its kernels share with nbx_binaries' -- per j tile TWO staged arrays, the
+    position records (zero padding behind n) and the velocity records of the same j, the j range in the splits of
+    diag_shape(n, n) -- so that the ways of pairing the two arrays wrongly may be planted: `fault`, one of TS_VELOCITY_FAULTS
+    (binaries_ref.velocity_map), `member0` as binaries_ref.restate's.  Without a fault: timescale_ref.timescale.  rows: the i side
+    is these bodies alone (each against all j)."""
+    assert fault is None or fault in TS_VELOCITY_FAULTS, fault
+    x = [np.asarray(state[f], dtype=np.float64) for f in POS]
+    v = [np.asarray(state[f], dtype=np.float64) for f in VEL]
+    gm = gm_as_uploaded(state["mass"])
+    n = len(gm)
+    _, tiles, _, per = diag_shape(n, n)
+    n_rec = tiles * BR.TILE
+    vp = [np.concatenate([c, np.zeros(n_rec - n)]) for c in v]
+    if fault == "velocity offset of the member not applied":
+        vp = [np.resize(np.concatenate([np.asarray(member0[f], dtype=np.float64), c]), n_rec) for f, c in zip(VEL, v)]
+    vmap = BR.velocity_map(n_rec, per, fault)
+    if vmap is not None:
+        vp = [np.where(vmap >= 0, c[np.maximum(vmap, 0)], 0.0) for c in vp]
+    out = {"approach_rate2": 0.0, "freefall_rate2": 0.0, "min_r2": np.inf}
+    rows = np.arange(n) if rows is None else np.asarray(rows, dtype=np.int64)
+    for lo in range(0, len(rows), chunk):
+        i = rows[lo:lo + chunk]
+        d = [c[None, :] - c[i, None] for c in x]
+        r2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + EPS2
+        w = [cj[None, :n] - c[i, None] for cj, c in zip(vp, v)]
+        approach = (w[0] * w[0] + w[1] * w[1] + w[2] * w[2]) / r2
+        freefall = (gm[None, :] + gm[i, None]) / (r2 * np.sqrt(r2))
+        own = (np.arange(len(i)), i)
+        approach[own], freefall[own], r2[own] = 0.0, 0.0, np.inf
+        out = {"approach_rate2": max(out["approach_rate2"], float(approach.max())), "freefall_rate2": max(out["freefall_rate2"], float(freefall.max())),
+               "min_r2": min(out["min_r2"], float(r2.min()))}
+    return out
 
 
 def timescale_background(precision):

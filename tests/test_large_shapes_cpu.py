@@ -5,6 +5,14 @@ tests/ragged_diag_plan_driver.cpp; and the sensitivity of the GPU module's compa
 restatements of neighbours_ref, paircount_ref, field_ref and potential_ref can plant, and a finish that adds only its first
 rows, must be rejected by the very functions the GPU module applies to the device's values.
 
+The lattice in Hubble flow (lattice_ref.hubble), which the GPU module runs nbx_timescale and nbx_binaries on: its closed forms
+against binaries_ref.binaries and timescale_ref.timescale by brute force at k = 5 and 13; that no shell of pairs lies inside the
+gate's window around e = 0; that binaries_ref.ambiguity flags only the exact ties of the face neighbours there; the row-sampled
+reference (rows=) against the full one, and the property binaries_ref.CLOUD_SEEDS[35937] was chosen for; and four ways of pairing
+the velocity tile with the wrong position record (binaries_ref.VELOCITY_FAULTS), planted in binaries_ref.restate and in
+lattice_ref.restate_timescale: rejected by the Hubble comparisons at k = 17 (the wrap at 65 536 at k = 41, on a few rows), and NOT
+seen by the comparison tests/test_binaries_gpu.py applies to the 13^3 lattice at rest -- the gap the Hubble shapes close.
+
 One entry of potential_ref.FAULTS, "velm read at the global index", is no fault of an unsliced launch -- with i_begin = 0 the
 local and the global index are one -- and the large shapes are unsliced: the test asserts that it changes no bit there
 (tests/test_potential_probe_cpu.py plants it on a slice)."""
@@ -16,6 +24,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import binaries_ref as BR
 import energy_ref as E
 import field_ref as FR
 import lattice_ref as L
@@ -132,6 +141,100 @@ def test_the_direct_field_truth_is_the_augmented_one(precision):
         assert (np.abs((a["phi"][0] - b["phi"][0]) + (a["phi"][1] - b["phi"][1])) <= tol * np.abs(a["phi"][0])).all()
 
 
+# ---- the lattice in Hubble flow ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", [5, NB.LATTICE_K])
+@pytest.mark.parametrize("precision", [32, 64])
+def test_hubble_closed_forms_against_brute_force(k, precision):
+    """fp64 against fp64 with the same formula: 1e-13 relative, the module's figure for such comparisons; partner and bound equal."""
+    for perm in (False, True):
+        for H in L.HUBBLE_H:
+            st = L.hubble(k, precision, perm, H)
+            for p, w in zip(NB.POS, L.VEL):
+                assert np.array_equal(st[w].astype(np.float64), H * st[p].astype(np.float64))
+            assert abs(L.hubble_gm(precision) - 1.0) <= 2.0 ** -23 and (st["mass"] == st["mass"][0]).all()
+            ref = BR.binaries(st, precision)
+            want = L.hubble_binaries_expected(k, H, precision, perm)
+            assert np.array_equal(ref["partner"], want["partner"]) and np.array_equal(ref["bound"], want["bound"]), (perm, H)
+            assert np.array_equal(ref["bound_lo"], ref["bound_hi"])  # no pair inside the window: the device is held to the exact count
+            assert (np.abs(ref["energy"] - want["energy"]) <= 1e-13 * abs(want["energy"])).all() and want["energy"] < 0
+            assert (np.abs(ref["mag"] - want["mag"]) <= 1e-13 * want["mag"]).all()
+            ts, tw = TS.timescale(st), L.hubble_timescale_expected(k, H, precision)
+            for f in TS.KEYS:
+                assert abs(ts[f] - tw[f]) <= 1e-13 * tw[f], (f, perm, H)
+            assert tw["approach_rate2"] < H * H  # the supremum of every true pair
+            assert L.restate_timescale(st) == {f: ts[f] for f in TS.KEYS}
+            assert G.check_hubble_binaries(BR.restate(st, precision), want, precision) <= 1e-3
+
+
+def test_no_shell_lies_inside_the_gate_window_around_zero_energy():
+    """(s_max, the relative margin |e| / (A + B) of the nearest shell) for every H: 3, 10 and 25, margins of 0.40 %, 0.43 % and
+    1.1 % -- four orders of magnitude outside 32 u (fp32); at H = 16 the bound sites are the 3 x 3 x 3 block about the body."""
+    table = {16.0: (3, 0.0040), 8.0: (10, 0.0043), 4.0: (25, 0.0112)}
+    assert set(L.HUBBLE_H) <= set(table)
+    for H, (s_max, margin) in table.items():
+        for precision in (32, 64):
+            for k in G.CONTEXT_K + tuple(G.MEMBER_K.values()) + (5, NB.LATTICE_K, K_FAULT):
+                got = L.hubble_shell(k, H, precision)
+                assert got[0] == s_max and abs(got[1] - margin) <= 1e-4, (H, precision, k, got)
+                assert got[1] > 1000 * BR.GATE[precision] * BR.U[precision]
+    for k, perm in ((5, True), (33, False)):
+        site = NB.lattice_order(k, perm)
+        a = [np.where((c == 0) | (c == k - 1), 2, 3) for c in (site // (k * k), (site // k) % k, site % k)]
+        assert np.array_equal(L.hubble_binaries_expected(k, 16.0, 32, perm)["bound"], a[0] * a[1] * a[2] - 1)
+
+
+@pytest.mark.parametrize("precision", [32, 64])
+def test_ambiguity_on_the_hubble_lattice_flags_only_exact_ties(precision):
+    """Every body has three or more face neighbours at ONE energy, so binaries_ref.ambiguity flags every body -- which is why the
+    partner is taken from the geometry there --, and nothing but those ties: the next shell's window ends far above e(1)'s."""
+    k = 5
+    g = BR.GATE[precision] * BR.U[precision]
+    for H in L.HUBBLE_H:
+        st = L.hubble(k, precision, True, H)
+        assert BR.ambiguity(st, precision) == k ** 3 == BR.ambiguity(st, precision, rows=np.arange(k ** 3))
+        e, mag = L.hubble_energy(np.array([1.0, 2.0]), H, precision)
+        assert e[1] - g * mag[1] > e[0] + g * mag[0] + 1.0  # the edge neighbours' window ends more than 1 above the face neighbours'
+        x = [st[f].astype(np.float64) for f in NB.POS]
+        d2 = sum((c[:, None] - c[None, :]) ** 2 for c in x)
+        faces = NB.lattice_expected(k, True)[1]
+        assert np.array_equal((d2 == 1.0 / 64).sum(axis=1), faces) and faces.min() >= 3  # the ties: three to six partners at e(1)
+        assert len(set(BR.binaries(st, precision)["energy"].tolist())) == 1
+
+
+def test_the_row_sampled_reference_is_the_full_one_on_those_rows():
+    n = 2049
+    rows = np.array([0, 5, 511, 512, 1279, 1280, 2048, 7])
+    for precision in (32, 64):
+        st = BR.cloud(n, precision)
+        full, part = BR.binaries(st, precision), BR.binaries(st, precision, rows=rows)
+        assert all(np.array_equal(part[f], full[f][rows]) for f in full)
+        assert BR.ambiguity(st, precision, rows=rows) == 0
+        rs, rp = BR.restate(st, precision), BR.restate(st, precision, rows=rows)
+        assert all(np.array_equal(rp[f], rs[f][rows]) for f in rs)
+        assert not BR.compare(rs, part, st, precision, rows=rows)[0] and not BR.compare(rs, full, st, precision)[0]
+        for fault in ("self not masked", "a split row dropped", "m_j alone instead of m_i + m_j", "velocity of record j + 1 read for record j"):
+            assert BR.compare(BR.restate(st, precision, fault=fault), part, st, precision, rows=rows)[0], fault
+
+
+@pytest.mark.parametrize("precision", [32, 64])
+def test_the_cloud_of_35937_has_no_ambiguous_sampled_row(precision):
+    """What binaries_ref.CLOUD_SEEDS[35937] was chosen for, from the reference alone: no sampled row ambiguous, none bound to
+    nobody or to everybody, so the device is held to partner EQUAL on every sampled row."""
+    n = G.CLOUD_N
+    rows = G.cloud_rows()
+    shape = FR.field_shape(n, n)
+    assert shape == G.REGIMES["k33"][1] and len(rows) == G.CLOUD_ROWS == len(set(rows.tolist())) and BR.CLOUD_SEEDS[n] == 100 + n % 97
+    columns, tiles, splits, per = shape
+    seams = {0, n - 1, 511, 512, 255, 256, (columns - 1) * 512 - 1, (columns - 1) * 512, per * 256 - 1, per * 256,
+             (splits - 1) * per * 256 - 1, (splits - 1) * per * 256, (splits // 2) * per * 256 - 1, (splits // 2) * per * 256}
+    assert seams <= set(rows.tolist())  # both sides of every probed column and split seam
+    st = BR.cloud(n, precision)
+    assert BR.ambiguity(st, precision, rows=rows) == 0
+    ref = BR.binaries(st, precision, rows=rows)
+    assert 0 < ref["bound"].min() and ref["bound"].max() < n - 1
+    assert ((ref["partner"] >= 0) & (ref["partner"] < n) & (ref["partner"] != rows)).all()
+
+
 # ---- the regime table ------------------------------------------------------------------------------------------------------------------
 def _build(tmp_path, name):
     exe = str(tmp_path / name)
@@ -174,6 +277,13 @@ def test_the_regime_table_is_the_headers(tmp_path):
         assert [tuple(s[:4]) for s in plan["shape"]] == [P.diag_shape(n, n) for n in sizes] and tuple(plan["shape"][1][:4]) == shape("k%d" % k)
         assert plan["shape"][1][4] > 256 and plan["shape"][0][4] == 1  # rows: the lattice against the member of five bodies
     assert 25 ** 3 <= 16383 < 26 ** 3 and 23 ** 3 <= 12288 < 24 ** 3  # the largest lattices a member holds
+    # the velocity-reading kernels and the tracers add no shape of their own: the Hubble lattices are k33, k81, k25 and k23, the
+    # cloud is k33's size, and the tracers' (n, m) are the field's (m, n), rows of the table above
+    assert G.CLOUD_N == G.REGIMES["k33"][0][0] and {c[0] for c in G.HUBBLE_CASES} == set(G.CONTEXT_K)
+    for name, (n, m) in G.TRACER_SHAPES.items():
+        assert G.REGIMES[name][0] == (m, n), name
+    assert all(G.REGIMES["field member fp%d" % p][0] == (G.TRACER_MEMBER_M, G.MEMBER_K[p] ** 3) for p in (32, 64)) and 2 * G.TRACER_MEMBER_M <= 2 ** 22
+    assert sorted(shape(name)[2] for name in G.TRACER_SHAPES) == [1, 15, 206] and shape("field one split")[0] == 1025  # tr_rows; columns
     G.test_every_kernel_family_meets_more_than_256_partial_rows()
 
 
@@ -229,6 +339,66 @@ def test_every_paircount_fault_is_rejected():
     # the large shapes' own: a finish that stops after the first rows (32 of 50 here, 256 of 1065 at k = 33)
     assert rejected(G.check_counts, PC.restate(st, G.RADII, precision, finish_rows=32), k)
     assert not rejected(G.check_counts, PC.restate(st, G.RADII, precision, finish_rows=50), k)
+
+
+WRAP_K = 41  # 68 921 bodies: the smallest lattice that has a record behind 65 536
+
+
+def wrap_rows(n):
+    return np.array([0, 1, 4095, 4096, BR.VELOCITY_WRAP - 1, BR.VELOCITY_WRAP, BR.VELOCITY_WRAP + 1, n - 1])
+
+
+@pytest.mark.parametrize("precision", [32, 64])
+def test_every_velocity_pairing_fault_is_rejected_in_hubble_flow_and_not_at_rest(precision):
+    """The four ways of pairing the velocity tile with the wrong position record: the comparisons the GPU module applies to a
+    lattice in Hubble flow reject each, in nbx_binaries' structure and in nbx_timescale's; the comparison of
+    tests/test_binaries_gpu.py on the lattice at rest, all there was above n = 4097, lets every one of them through."""
+    k = K_FAULT
+    assert FR.field_shape(k ** 3, k ** 3) == P.diag_shape(k ** 3, k ** 3) == (10, 20, 5, 4)
+    small = [f for f in BR.VELOCITY_FAULTS if f != "velocity index wraps at 65 536"]
+    for perm, H, kernels in ((False, 16.0, "both"), (True, 8.0, "binaries"), (True, 16.0, "timescale")):  # the timescale cases all have H = 16
+        st = L.hubble(k, precision, perm, H)
+        other = L.hubble(k, precision, not perm, L.HUBBLE_H[1] if H == L.HUBBLE_H[0] else L.HUBBLE_H[0])  # the member before it
+        want = L.hubble_binaries_expected(k, H, precision, perm)
+        tw = L.hubble_timescale_expected(k, H, precision)
+        if kernels != "timescale":
+            G.check_hubble_binaries(BR.restate(st, precision), want, precision)
+        if kernels != "binaries":
+            G.check_timescale(L.restate_timescale(st), tw, precision)
+        for fault in small:
+            if kernels != "timescale":
+                got = BR.restate(st, precision, fault=fault, member0=other)
+                assert rejected(G.check_hubble_binaries, got, want, precision), (perm, H, fault)
+            if kernels != "binaries":
+                ts = L.restate_timescale(st, fault=fault, member0=other)
+                assert rejected(G.check_timescale, ts, tw, precision), (perm, fault)
+                assert ts["approach_rate2"] > H * H  # above the supremum of every true pair
+    # the wrap shows behind 65 536 records alone: k = 41 on a few rows, each against all j
+    n = WRAP_K ** 3
+    rows = wrap_rows(n)
+    fault = "velocity index wraps at 65 536"
+    for perm in (False, True):
+        st = L.hubble(WRAP_K, precision, perm, 16.0)
+        want = L.hubble_binaries_expected(WRAP_K, 16.0, precision, perm)
+        G.check_hubble_binaries(BR.restate(st, precision, rows=rows), want, precision, rows=rows)
+        assert rejected(G.check_hubble_binaries, BR.restate(st, precision, rows=rows, fault=fault), want, precision, rows)
+        tw = L.hubble_timescale_expected(WRAP_K, 16.0, precision)
+        corners = np.flatnonzero(np.isin(NB.lattice_order(WRAP_K, perm), [0, n - 1]))  # the two bodies of the extreme pair
+        G.check_timescale(L.restate_timescale(st, rows=corners), tw, precision)
+        assert rejected(G.check_timescale, L.restate_timescale(st, rows=np.concatenate([corners, rows]), fault=fault), tw, precision)
+    # at rest: the device test of the 13^3 lattice cannot see any of them -- the gap these shapes close
+    for perm in (False, True):
+        st = BR.lattice(precision, perm)
+        want = BR.binaries(st, precision)
+        want["partner"] = NB.lattice_expected(BR.LATTICE_K, perm)[0]
+        clean = BR.restate(st, precision)
+        for fault in small:
+            got = BR.restate(st, precision, fault=fault, member0=st)
+            assert not BR.differs(got, want, st, precision), (perm, fault)
+            assert all(np.array_equal(got[f], clean[f]) for f in BR.KEYS)
+    # and the members' own cloud comparison does see a member that reads the first member's velocities
+    a, b = BR.cloud(513, precision), BR.cloud(1025, precision)
+    assert BR.differs(BR.restate(b, precision, fault="velocity offset of the member not applied", member0=a), BR.binaries(b, precision), b, precision)
 
 
 @pytest.mark.parametrize("precision", [32, 64])

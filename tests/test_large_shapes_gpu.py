@@ -1,5 +1,5 @@
-"""The pair-work analysis kernels -- the potential of nbx_diagnostics, nbx_timescale, nbx_field, nbx_neighbours, nbx_paircount and
-their ensemble and ragged forms -- at the launch shapes the other device modules never reach (they stop at n = 4099: nine
+"""The pair-work analysis kernels -- the potential of nbx_diagnostics, nbx_timescale, nbx_field, nbx_neighbours, nbx_paircount,
+nbx_binaries, the pair loop and update of nbx_tracers, and their ensemble and ragged forms -- at the launch shapes the other device modules never reach (they stop at n = 4099: nine
 columns, four splits), against references that do not cost O(n^2): the closed forms of tests/lattice_ref.py on a cubic lattice
 of equal masses, and row-sampled high-precision sums.
 
@@ -29,6 +29,30 @@ K_ref is the CPU oracle's (acceleration) and the sequential sum's (potential) on
 narrow the gate; and with the k = 33 lattice as bodies and its own sites as points, 1/2 sum m phi_i plus the self terms is
 lattice_ref.potential within (256 t + 17) u, t = 10 the tiles of a split that field_body adds in T.
 
+The velocity-reading kernels.  nbx_timescale and nbx_binaries stage a SECOND tile, the velocity records of the same j.  A lattice
+at rest holds zero in every velocity record (but the planted body's), so a kernel that pairs a velocity with the wrong position --
+record j + 1, the first split's tile in every split, a member's offset applied to one buffer alone, an index that wraps at 2^16 --
+returns the same values there: tests/test_large_shapes_cpu.py shows that the comparison of tests/test_binaries_gpu.py on the 13^3
+lattice at rest lets each of these through.  So the lattices also run in Hubble flow (lattice_ref.hubble: v = H x, H = 16 or 8,
+every mass 1 / G): every velocity is exact, dv = H dx exactly and every pair value is a function of the squared lattice radius s.
+timescale: the rates within 32 u / 128 u and min_r2 within 8 u of lattice_ref.hubble_timescale_expected, O(1) -- the approach rate
+H^2 D^2 / (D^2 + eps^2) of the corner-to-corner pair stays below H^2, which a far mispairing exceeds.  binaries: e(s) grows with s,
+so partner EQUALS the geometry's lowest-numbered face neighbour, energy is one bit pattern within binaries_ref.GATE u (A + B) of
+e(1), and bound EQUALS the number of sites within s <= 3 (H = 16) or s <= 10 (H = 8), exact integers -- the nearest shell is 0.40 %
+of A + B from e = 0 -- that change when a pair's velocity is another record's; bound=False returns the same partner and energy
+bits and binaries_ref.identities holds.  At k = 33 and k = 81 (partner indices above 2^16, one split walking 2076 tiles), natural
+and permuted; as an ensemble of two such lattices of DIFFERENT H and as ragged members among clouds of 5 and 8192 bodies, every
+member also bit for bit a context of its state.  A cloud of 35 937 bodies (binaries_ref.cloud, its seed chosen on the CPU so that
+no sampled row is ambiguous): binaries_ref.compare on 1000 rows -- seam_bodies', both sides of the probed column and split seams
+among them -- against the row-sampled reference, and on EVERY body, in O(n), energy within the gate of the fp64 energy of the pair
+(i, partner[i]) and energy[partner[i]] <= energy[i] + that window; the worst value goes to profiles/binaries_error.json.
+
+The tracers.  tests/test_tracers_gpu.py stops at (n, m) = (4099, 513): the tracers' own partial rows [systems][tr_rows][m] have met
+4 rows and 3 columns.  Here: (262 657, 300), one column and 206 rows; (32 769, 32 769), 65 x 15; (257, 524 289), 1025 columns, the
+last of one tracer; two members with 65 537 tracers each.  Two steps, then one -- the second call starts on the other position
+buffer -- then a kick, at dt = 0.01, bit for bit tracers_ref.round_trip / round_trip_kick on a twin, the bodies bit for bit plain
+step's.  No tolerance is needed: nbx_field is held to field_ref.truth_at at exactly these shapes by this module.
+
 Every case's shape, worst deviation, gate, largest count and time go to large_shapes.json in the GPU suite's report directory
 (OUT of tests/test_parity_gpu.py).
 
@@ -42,7 +66,16 @@ point's sum has 512 terms and K_ref stays under the floor: K 21.1 (acceleration)
 19.0 in fp64; elsewhere K <= 25.1 under gates of 84 and more; the lattice's own sites 4.3 u (fp32) and 18.4 u (fp64) of 2577.  One call at k = 81,
 fp32 / fp64: neighbours 0.11 / 0.15 s, potential 0.064 / 0.134 s, timescale 0.12 / 0.29 s, paircount of twenty radii 0.59 / 0.60 s
 -- no case needed the drop to k = 80; the slowest tests, the heavy-body sweep and paircount at k = 81 in fp64, take 3.7 s, the
-module about a minute.
+module about a minute.  When the velocity-reading kernels and the tracers were added to it (nbx_binaries had met no reference above
+n = 4097, no velocity tile anything but zeros at scale, the tracers no more than 4 partial rows): again nothing failed and no
+kernel was changed.  timescale in Hubble flow: approach rate 1.1 u of 32 (fp32) and 2.0 u of 128 (fp64) at k = 81, 0.48 u and
+1.0 u at k = 33, free-fall rate 0.64 u and 1.1 u, min_r2 0.12 u and exact; one call at k = 81 0.12 / 0.27 s.  binaries in Hubble
+flow: partner and bound equal on every body of every case (bound up to 26 at H = 16, 146 at H = 8), energy 0.23 u (H = 16) and
+0.26 u (H = 8) of 32 in fp32, exact in fp64; one call at k = 81 0.145 / 0.267 s, at k = 33 0.8 / 1.3 ms.  The cloud: every
+sampled partner equal, every bound inside its bracket (895 of the 1000 brackets are one integer in fp32, all in fp64), energy
+3.2 u of 32 (fp32) and 32.3 u of 128 (fp64) over all 35 937 bodies, a little above the 2.8 u and 30.0 u seen up to n = 4097 and
+under the header's first-order 6.5 u and 55.5 u.  The members: the contexts' bits and the same deviations.  The tracers: every
+bit equal; the two steps at (262 657, 300) take 0.044 / 0.079 s.  The additions take about six seconds.
 """
 import json
 import math
@@ -54,12 +87,15 @@ import time
 import numpy as np
 import pytest
 
+import binaries_ref as BR
 import field_ref as FR
 import force_ref as F
+import kick_ref as K
 import lattice_ref as L
 import neighbours_ref as NB
 import paircount_ref as PC
 import potential_ref as P
+import tracers_ref as TR
 from conftest import PKG, ROOT
 from energy_ref import EPS2, gm_as_uploaded
 
@@ -200,6 +236,70 @@ def check_field(result, case, precision):
     assert ka <= case["gate_acc"], ("acc", ka, case["gate_acc"])
     assert kp <= case["gate_phi"], ("phi", kp, case["gate_phi"])
     return ka, kp
+
+
+# ---- the lattice in Hubble flow, and the cloud ------------------------------------------------------------------------------------------
+HUBBLE_CASES = [(k, H, precision, perm) for k, H in ((33, 16.0), (33, 8.0), (81, 16.0)) for precision in (32, 64) for perm in (False, True)]
+hubble_name = lambda c: "k%d-H%d-fp%d-%s" % (c[0], c[1], c[2], "permuted" if c[3] else "natural")
+CLOUD_N = 35937
+CLOUD_ROWS = 1000
+TRACER_DT = 0.01  # tests/test_tracers_gpu.py's: no power of two, so a contracted a dt + w would show
+# (n, m) of the tracer cases by the entry of REGIMES that is field_shape(m, n): the field's own extreme shapes
+TRACER_SHAPES = {"field one column": (262657, 300), "field target": (32769, 32769), "field one split": (257, 524289)}
+TRACER_MEMBER_M = 65537
+
+
+def hubble(k, precision, perm, H):
+    return cached(("hubble", k, precision, perm, H), lambda: L.hubble(k, precision, perm, H))
+
+
+def hubble_binaries(k, H, precision, perm):
+    return cached(("hubble binaries", k, H, precision, perm), lambda: L.hubble_binaries_expected(k, H, precision, perm))
+
+
+def check_hubble_binaries(got, want, precision, rows=None):
+    """partner and bound EQUAL lattice_ref.hubble_binaries_expected on every body (of `rows`, where `got` holds those bodies
+    alone), energy one bit pattern within binaries_ref.GATE u (A + B) of e(1).  Returns the deviation of energy in u (A + B)."""
+    pick = (lambda a: a) if rows is None else (lambda a: a[np.asarray(rows)])
+    for f in ("partner", "bound"):
+        g, w = np.asarray(got[f]), pick(want[f])
+        assert g.shape == w.shape, (f, g.shape, w.shape)
+        bad = np.flatnonzero(g != w)
+        assert bad.size == 0, (f, bad.size, bad[:8].tolist(), g[bad[:8]].tolist(), w[bad[:8]].tolist())
+    e = np.asarray(got["energy"])
+    assert (bits(e) == bits(e)[0]).all(), ("energy bits differ", np.flatnonzero(bits(e) != bits(e)[0])[:8].tolist())
+    dev = abs(float(e[0]) - want["energy"]) / (U[precision] * want["mag"])
+    assert dev <= BR.GATE[precision], dev
+    return dev
+
+
+def cloud(precision):
+    return cached(("cloud", precision), lambda: BR.cloud(CLOUD_N, precision))
+
+
+def cloud_rows():
+    """The bodies of the cloud the row-sampled reference is asked for: seam_bodies' -- first, last, both sides of the probed column
+    and split seams -- filled up to CLOUD_ROWS with seeded random ones.  binaries_ref.CLOUD_SEEDS[35937] was chosen for them."""
+    return np.array(seam_bodies(CLOUD_N, FR.field_shape(CLOUD_N, CLOUD_N), count=CLOUD_ROWS), dtype=np.int64)
+
+
+def check_cloud(got, state, precision, want, rows):
+    """binaries_ref.compare on the sampled rows, and on ALL bodies in O(n): energy[i] within the gate of the fp64 energy of the
+    pair (i, partner[i]), and energy[partner[i]] <= energy[i] + that pair's window (j's minimum is at most its pair with i).
+    Returns the largest energy deviation in u (A + B)."""
+    n = len(state["mass"])
+    problems, worst = BR.compare(got, want, state, precision, rows=rows)
+    assert not problems, problems
+    p, e = np.asarray(got["partner"]), np.asarray(got["energy"], dtype=np.float64)
+    i = np.arange(n)
+    assert p.shape == (n,) and ((p >= 0) & (p < n) & (p != i)).all()
+    e_own, mag = BR.pair_energy(state, i, p)
+    dev = np.abs(e - e_own) / (U[precision] * mag)
+    assert dev.max() <= BR.GATE[precision], (int(dev.argmax()), float(dev.max()))
+    window = BR.GATE[precision] * U[precision] * mag
+    late = np.flatnonzero(~(e[p] <= e + window))
+    assert late.size == 0, (late.size, late[:8].tolist())
+    return max(worst, float(dev.max()))
 
 
 # ---- the heavy body on the lattice -----------------------------------------------------------------------------------------------------
@@ -393,7 +493,136 @@ def test_timescale_of_a_context_with_one_planted_body(nbx, case):
     record(kernel="timescale", case=case_name(case), shape=shape_of(k), worst_u=worst, rate_gate_u=RATE_GATE[precision], r2_gate_u=R2_GATE, call_s=seconds)
 
 
+# ---- the velocity-reading kernels ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CONTEXT_CASES, ids=case_name)
+def test_timescale_of_a_lattice_in_hubble_flow(nbx, case):
+    k, precision, perm = case
+    H = L.HUBBLE_H[0]
+    with nbx.Context(k ** 3, precision) as c:
+        c.upload(hubble(k, precision, perm, H))
+        c.sync()
+        t0 = time.perf_counter()
+        got = c.timescale()
+        seconds = time.perf_counter() - t0
+        devs = check_timescale(got, L.hubble_timescale_expected(k, H, precision), precision)
+        assert c.timescale() == got  # the same call twice: the same bits
+        c.step(1, STEP_DT / 4, kenergy=False)
+        moved = c.timescale()
+        assert moved["steps_done"] == 1 and all(moved[f] != got[f] for f in ("approach_rate2", "freefall_rate2", "min_r2")) and c.timescale() == moved
+    record(kernel="timescale, Hubble flow", case=case_name(case), shape=shape_of(k), H=H, worst_u=devs, rate_gate_u=RATE_GATE[precision],
+           r2_gate_u=R2_GATE, call_s=seconds)
+
+
+@pytest.mark.parametrize("case", HUBBLE_CASES, ids=hubble_name)
+def test_binaries_of_a_lattice_in_hubble_flow(nbx, case):
+    k, H, precision, perm = case
+    want = hubble_binaries(k, H, precision, perm)
+    with nbx.Context(k ** 3, precision) as c:
+        c.upload(hubble(k, precision, perm, H))
+        c.sync()
+        t0 = time.perf_counter()
+        got = c.binaries()
+        seconds = time.perf_counter() - t0
+        plain = c.binaries(bound=False)  # the kernels compiled without the count
+    dev = check_hubble_binaries(got, want, precision)
+    assert plain["bound"] is None and all(np.array_equal(bits(plain[f]), bits(got[f])) for f in ("partner", "energy"))
+    assert not BR.identities(got), BR.identities(got)
+    record(kernel="binaries, Hubble flow", case=hubble_name(case), shape=shape_of(k), H=H, energy_u=dev, gate_u=BR.GATE[precision],
+           largest_bound=int(got["bound"].max()), call_s=seconds)
+
+
+@pytest.mark.parametrize("precision", [32, 64])
+def test_binaries_of_a_cloud_on_sampled_rows_and_on_every_body(nbx, precision):
+    import test_binaries_gpu as BG  # the recorder of profiles/binaries_error.json
+    st, rows = cloud(precision), cloud_rows()
+    want = cached(("cloud reference", precision), lambda: BR.binaries(st, precision, rows=rows))
+    assert BR.ambiguity(st, precision, rows=rows[:64]) == 0  # the seed's property, re-checked on a part (the CPU module checks all rows)
+    with nbx.Context(CLOUD_N, precision) as c:
+        c.upload(st)
+        c.sync()
+        t0 = time.perf_counter()
+        got = c.binaries()
+        seconds = time.perf_counter() - t0
+        assert all(np.array_equal(bits(a), bits(b)) for a, b in zip(c.binaries().values(), got.values()))
+    worst = check_cloud(got, st, precision, want, rows)
+    assert not BR.identities(got), BR.identities(got)
+    sampled = got["bound"][rows]
+    assert 0 < sampled.min() and sampled.max() < CLOUD_N - 1
+    BG.note_worst(precision, worst, CLOUD_N, "cloud")
+    record(kernel="binaries, cloud", case="fp%d" % precision, shape=shape_of(33), rows_checked=len(rows), energy_u=worst, gate_u=BR.GATE[precision],
+           bound_exact_by_the_reference=int((want["bound_lo"] == want["bound_hi"]).sum()), call_s=seconds)
+
+
 # ---- members -------------------------------------------------------------------------------------------------------------------------------
+def velocity_context(nbx, state, precision):
+    """(timescale, binaries) of a context of the state's size holding it."""
+    with nbx.Context(len(state["mass"]), precision) as c:
+        c.upload(state)
+        return c.timescale(), c.binaries()
+
+
+def same_binaries(a, b):
+    return all(np.array_equal(bits(a[f]), bits(b[f])) for f in BR.KEYS)
+
+
+def same_timescale(a, b):
+    return all(a[f] == b[f] for f in ("approach_rate2", "freefall_rate2", "min_r2"))
+
+
+@pytest.mark.parametrize("precision", [32, 64])
+def test_velocity_reading_members_of_an_ensemble(nbx, precision):
+    """Two lattices in Hubble flow of DIFFERENT H, so that a member that reads the other's velocities shows."""
+    k = MEMBER_K[precision]
+    n = k ** 3
+    members = ((L.HUBBLE_H[0], False), (L.HUBBLE_H[1], True))
+    states = [hubble(k, precision, perm, H) for H, perm in members]
+    with nbx.Ensemble(n, 2, precision) as e:
+        e.upload(states)
+        ts, b = e.timescale(), e.binaries()
+        assert all(np.array_equal(bits(x), bits(y)) for x, y in zip(e.binaries().values(), b.values()))
+        plain = e.binaries(bound=False)
+        assert plain["bound"] is None and all(np.array_equal(bits(plain[f]), bits(b[f])) for f in ("partner", "energy"))
+        for m, (H, perm) in enumerate(members):
+            got = {f: b[f][m] for f in BR.KEYS}
+            tdev = check_timescale(ts[m], L.hubble_timescale_expected(k, H, precision), precision)
+            dev = check_hubble_binaries(got, hubble_binaries(k, H, precision, perm), precision)
+            assert not BR.identities(got)
+            cts, cb = velocity_context(nbx, states[m], precision)
+            assert same_timescale(ts[m], cts) and same_binaries(got, cb), m
+            record(kernel="ensemble member, Hubble flow", case=hubble_name((k, H, precision, perm)), shape=shape_of(k), timescale_u=tdev, energy_u=dev,
+                   gate_u=BR.GATE[precision])
+        one = e.binaries(first=1, count=1)  # a launch that starts at the second member
+        assert all(np.array_equal(bits(one[f][0]), bits(b[f][1])) for f in BR.KEYS)
+
+
+def small_cloud(n, precision):
+    return cached(("small cloud", n, precision), lambda: BR.cloud(n, precision, seed=100 + n % 97))
+
+
+@pytest.mark.parametrize("precision", [32, 64])
+def test_velocity_reading_members_of_a_ragged_ensemble_among_small_ones(nbx, precision):
+    k = MEMBER_K[precision]
+    n = k ** 3
+    sizes = (SMALL_MEMBERS[0], n, SMALL_MEMBERS[1], n)
+    members = {1: (L.HUBBLE_H[0], False), 3: (L.HUBBLE_H[1], True)}
+    states = [small_cloud(sizes[0], precision), hubble(k, precision, *members[1][::-1]), small_cloud(sizes[2], precision),
+              hubble(k, precision, *members[3][::-1])]
+    with nbx.Ragged(sizes, precision) as r:
+        r.upload(states)
+        ts, b = r.timescale(), r.binaries()
+        assert all(same_binaries(x, y) for x, y in zip(r.binaries(), b)) and all(same_timescale(x, y) for x, y in zip(r.timescale(), ts))
+        for m in range(4):  # every member, the small ones that leave the grid early included, has the bits of a context of its size
+            cts, cb = velocity_context(nbx, states[m], precision)
+            assert same_timescale(ts[m], cts) and same_binaries(b[m], cb), m
+        for m, (H, perm) in members.items():
+            tdev = check_timescale(ts[m], L.hubble_timescale_expected(k, H, precision), precision)
+            dev = check_hubble_binaries(b[m], hubble_binaries(k, H, precision, perm), precision)
+            assert not BR.identities(b[m])
+            record(kernel="ragged member, Hubble flow", case=hubble_name((k, H, precision, perm)), shape=shape_of(k), timescale_u=tdev, energy_u=dev,
+                   gate_u=BR.GATE[precision])
+        assert same_binaries(r.binaries(first=3, count=1)[0], b[3]) and same_binaries(r.binaries(first=0, count=1)[0], b[0])
+
+
 def small_member(n, precision):
     return cached(("small", n, precision), lambda: NB.member(n, precision))
 
@@ -582,6 +811,84 @@ def test_the_field_at_the_lattices_own_sites_adds_up_to_the_closed_form(nbx, pre
     assert dev <= gate, (dev, gate)
 
 
+# ---- the tracers at the field's extreme shapes ---------------------------------------------------------------------------------------------
+def tracer_case(precision, n, m, seed=0):
+    def make():
+        state = K.make_state(9100 + 7 * seed + n % 1000, n, NB.DTYPE[precision])
+        return state, TR.make_tracers(precision, state, m, seed=seed)
+    return cached(("tracers", precision, n, m, seed), make)
+
+
+def split_tracers(tr):
+    return [tr[f] for f in TR.POS], [tr[f] for f in TR.VEL]
+
+
+def stacked(dicts):
+    return {f: np.ascontiguousarray(np.stack([d[f] for d in dicts])) for f in TR.KEYS}
+
+
+def bodies_same(a, b):
+    """Two downloads of one kind of object: a dict of arrays, or a list of them."""
+    return all(TR.same(x, y) for x, y in zip(a, b)) if isinstance(a, list) else TR.same(a, b)
+
+
+def run_tracers(o, twin, state, tr, precision):
+    """Two steps, then one -- the second call starts on the other position buffer -- then one kick, on `o`, against the round
+    trip on `twin`, an object of the same kind that holds the same bodies: nbx_field at the host's tracer positions, the update
+    in numpy, one plain step.  Bit for bit, the bodies included.  Returns the seconds of the first tracers_step call."""
+    h = 0.37 * TRACER_DT
+    for obj in (o, twin):
+        obj.upload(state)
+    want, ke_want = TR.round_trip(twin, tr, precision, TRACER_DT, 3)
+    o.tracers_upload(*split_tracers(tr))
+    o.sync()
+    t0 = time.perf_counter()
+    o.tracers_step(2, TRACER_DT, kenergy=False)
+    o.sync()
+    seconds = time.perf_counter() - t0
+    ke = o.tracers_step(1, TRACER_DT)
+    got = o.tracers_download()
+    assert TR.same(got, want) and not TR.same(want, tr)
+    assert bodies_same(o.download(), twin.download()) and np.array_equal(ke, ke_want)  # the bodies are plain step's
+    kicked = TR.round_trip_kick(twin, got, precision, h)
+    o.tracers_kick(h)
+    after = o.tracers_download()
+    assert TR.same(after, kicked) and not TR.same(after, got)
+    assert all(np.asarray(after[f]).tobytes() == np.asarray(got[f]).tobytes() for f in TR.POS)
+    return seconds
+
+
+@pytest.mark.parametrize("name", list(TRACER_SHAPES), ids=[n.replace(" ", "-") for n in TRACER_SHAPES])
+@pytest.mark.parametrize("precision", [32, 64])
+def test_tracers_of_a_context_at_the_fields_extreme_shapes(nbx, precision, name):
+    """No tolerance: nbx_field is held to field_ref.truth_at at exactly these shapes (test_the_field_of_a_context), and the
+    tracers are held to nbx_field's bits -- what is new here is the tracers' own partial-row buffer [tr_rows][tr_m], up to 206 rows
+    and 1025 columns where tests/test_tracers_gpu.py reaches 4 and 3, and the update launch that adds the rows in place."""
+    n, m = TRACER_SHAPES[name]
+    assert REGIMES[name][0] == (m, n)
+    state, tr = tracer_case(precision, n, m)
+    with nbx.Context(n, precision) as c, nbx.Context(n, precision) as twin:
+        seconds = run_tracers(c, twin, state, tr, precision)
+        assert c.tracers_count() == m and c.stats()["steps_done"] == 3
+    record(kernel="tracers", case="%s fp%d" % (name, precision), shape=REGIMES[name][1], n=n, m=m, two_steps_s=seconds)
+
+
+@pytest.mark.parametrize("precision", [32, 64])
+def test_tracers_of_two_members_at_65537_tracers_each(nbx, precision):
+    """As above for an ensemble of two members of the largest lattice size a member holds, 2 x 65 537 tracers: the twin is an
+    ensemble too, and nbx_ensemble_field is held to the truth at this shape by test_the_field_of_a_member."""
+    name = "field member fp%d" % precision
+    (m, n), shape = REGIMES[name][:2]
+    assert m == TRACER_MEMBER_M and n == MEMBER_K[precision] ** 3 and 2 * m <= 2 ** 22
+    cases = [tracer_case(precision, n, m, seed=1 + j) for j in range(2)]
+    states, tr = [c[0] for c in cases], stacked([c[1] for c in cases])
+    with nbx.Ensemble(n, 2, precision) as e, nbx.Ensemble(n, 2, precision) as twin:
+        seconds = run_tracers(e, twin, states, tr, precision)
+        got = e.tracers_download()
+        assert all(got[f].shape == (2, m) for f in TR.KEYS) and not TR.same({f: got[f][0] for f in TR.KEYS}, {f: got[f][1] for f in TR.KEYS})
+    record(kernel="tracers", case="two members fp%d" % precision, shape=shape, n=n, m=m, two_steps_s=seconds)
+
+
 # ---- what the shapes reach ---------------------------------------------------------------------------------------------------------------
 def test_every_kernel_family_meets_more_than_256_partial_rows():
     """The potential's, the timescale's and the pair counts' reduce walk splits x columns rows in strides of 256; neighbours and
@@ -591,3 +898,8 @@ def test_every_kernel_family_meets_more_than_256_partial_rows():
         assert (columns, tiles, splits, per) == FR.field_shape(k ** 3, k ** 3) == REGIMES["k%d" % k][1]
         assert columns * splits > 256, (k, columns, splits)  # potential, timescale, paircount: contexts and members of both precisions
     assert max(FR.field_shape(*REGIMES[name][0])[2] for name in REGIMES if name.startswith("field")) == 206
+    # nbx_binaries' finish is of the second kind -- one thread per body walks that body's split rows in ascending order
+    # (csrc/nbx_binaries_kernels.hpp: bound_finish_kernel), no stride of 256 --: 15 rows in the target regime, one at k = 81; the
+    # tracers' update launch adds a tracer's tr_rows partial rows the same way, 206 of them at (n, m) = (262 657, 300)
+    assert [FR.field_shape(k ** 3, k ** 3)[2] for k in CONTEXT_K] == [15, 1] and FR.field_shape(CLOUD_N, CLOUD_N)[2] == 15
+    assert max(FR.field_shape(m, n)[2] for n, m in TRACER_SHAPES.values()) == 206
