@@ -151,6 +151,13 @@ struct Object {
   void* nl_r2 = nullptr;
   void* nl_tab = nullptr;
   size_t nl_seg_cap = 0, nl_scan_cap = 0, nl_index_cap = 0, nl_r2_cap = 0;
+  // accelerations and their time derivatives (nbx_jerk.hip): the partial rows (two records per body and split) and the result
+  // records (two per body), allocated on first use and grown likewise (sizes in bytes); jerk_tab: a ragged ensemble's
+  // {pos_off, vel_off, out_off, n} per member, built on first use
+  void* jerk_part = nullptr;
+  void* jerk_out = nullptr;
+  void* jerk_tab = nullptr;
+  size_t jerk_part_cap = 0, jerk_out_cap = 0;
   // resident tracers (nbx_tracers.hip): tr_m per system (0: none), every system's {x, y, z, 0} position and velocity records
   // one system after the other, and the partial rows of the pair work ([systems][tr_rows][tr_m] records, buffers of their own:
   // not the field's scratch), allocated by the first upload and grown likewise (sizes in bytes); tr_have: per system, its
@@ -365,7 +372,7 @@ inline void batch_release(Object* o) {
                   o->pc_out, o->pc_tab, o->knn_part, o->knn_out, o->knn_tab, o->fof_rec, o->fof_part,
                   o->fof_work, o->fof_out, o->fof_tab, o->bin_part, o->bin_out, o->bin_tab, o->tidal_pts, o->tidal_part,
                   o->tidal_out, o->tidal_tab, o->clump_lab, o->clump_part, o->clump_out, o->clump_tab, o->nl_seg, o->nl_scan, o->nl_index,
-                  o->nl_r2, o->nl_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
+                  o->nl_r2, o->nl_tab, o->jerk_part, o->jerk_out, o->jerk_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
     if (p) (void)hipFree(p);
   if (o->own_stream) (void)hipStreamDestroy(o->stream);
 }

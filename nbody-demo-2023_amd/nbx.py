@@ -108,6 +108,9 @@ NLIST_KEYS = ("offsets", "index", "r2", "total")
 NLIST_MAX_CAPACITY = 1 << 28  # entries per call
 NLIST_FIRST_GUESS = 16        # entries per body nlist() tries before it asks again with the exact total
 GRAV = float(np.float32(6.67259e-11))  # the library's G: (float)6.67259e-11f, widened
+# the symbols of include/nbx_jerk.h (the acceleration of every body and its time derivative), kept apart likewise
+JERK_SYMBOLS = ("nbx_jerk", "nbx_ensemble_jerk", "nbx_ragged_jerk")
+JERK_KEYS = ("acc_x", "acc_y", "acc_z", "jerk_x", "jerk_y", "jerk_z")
 
 
 class NbxError(RuntimeError):
@@ -175,6 +178,11 @@ class ClumpsOut(ctypes.Structure):
     """nbx_clumps_out_t (include/nbx_clumps.h): every pointer may be NULL."""
     _fields_ = [("members", ctypes.c_void_p), ("gm", ctypes.c_void_p), ("centre", ctypes.c_void_p * 3), ("velocity", ctypes.c_void_p * 3),
                 ("phi", ctypes.c_void_p), ("energy", ctypes.c_void_p)]
+
+
+class JerkOut(ctypes.Structure):
+    """nbx_jerk_out_t (include/nbx_jerk.h): every pointer may be NULL."""
+    _fields_ = [("acc", ctypes.c_void_p * 3), ("jerk", ctypes.c_void_p * 3)]
 
 
 class EnsembleStats(ctypes.Structure):
@@ -353,6 +361,10 @@ def load():
         L.nbx_nlist.argtypes = [vp, dbl, i64, vp, vp, vp, vp]
         L.nbx_ensemble_nlist.argtypes = [vp, i32, i32, dbl, i64, vp, vp, vp, vp]
         L.nbx_ragged_nlist.argtypes = [vp, i32, i32, dbl, i64, vp, vp, vp, vp]
+    if hasattr(L, "nbx_jerk"):  # likewise for nbx_jerk.hip
+        L.nbx_jerk.argtypes = [vp, ctypes.POINTER(JerkOut)]
+        L.nbx_ensemble_jerk.argtypes = [vp, i32, i32, ctypes.POINTER(JerkOut)]
+        L.nbx_ragged_jerk.argtypes = [vp, i32, i32, ctypes.POINTER(JerkOut)]
     _lib = L
     return L
 
@@ -631,6 +643,91 @@ def unbind(obj, label, max_iter=32):
     return label, result, iterations
 
 
+def _jerk_arrays(shape, dtype):
+    """(the six result arrays of a *_jerk call by key, the nbx_jerk_out_t that points at them)."""
+    out = {k: np.zeros(shape, dtype=dtype) for k in JERK_KEYS}
+    a = [out[k].ctypes.data for k in JERK_KEYS]
+    return out, JerkOut((ctypes.c_void_p * 3)(*a[:3]), (ctypes.c_void_p * 3)(*a[3:]))
+
+
+def jerk_dt(result, eta):
+    """The first-order time-step criterion per body from one jerk() result (a dict of the six JERK_KEYS arrays, any shape):
+    eta |a| / |adot| in fp64, +inf where |adot| = 0."""
+    r = {k: np.asarray(result[k], dtype=np.float64) for k in JERK_KEYS}
+    a = np.sqrt(r["acc_x"] ** 2 + r["acc_y"] ** 2 + r["acc_z"] ** 2)
+    j = np.sqrt(r["jerk_x"] ** 2 + r["jerk_y"] ** 2 + r["jerk_z"] ** 2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(j > 0.0, float(eta) * a / j, np.inf)
+
+
+def _remember_mass(obj, first, masses):
+    """upload() keeps the masses it was given, per member: the library returns positions and velocities only, and hermite()
+    uploads states of its own."""
+    if not hasattr(obj, "_mass"):
+        obj._mass = {}
+    for k, m in enumerate(masses):
+        obj._mass[first + k] = np.array(m, dtype=obj.dtype)
+
+
+def _hermite_io(obj):
+    """(download, upload, jerk, masses) of the object as lists of per-system dicts (an ensemble: one dict of (members, n) arrays)."""
+    if not isinstance(obj, (Context, Ensemble, Ragged)):
+        raise NbxError(NBX_ERR_ARG, "hermite", "expected a Context, an Ensemble or a Ragged")
+    members = 1 if isinstance(obj, Context) else obj.members
+    kept = getattr(obj, "_mass", {})
+    for k in range(members):
+        if k not in kept:
+            raise NbxError(NBX_ERR_STATE, "hermite", "member %d has not been uploaded through this object: its masses are not known" % k)
+    if isinstance(obj, Ragged):
+        return obj.download, obj.upload, obj.jerk, [kept[k] for k in range(members)]
+    mass = kept[0] if isinstance(obj, Context) else np.stack([kept[k] for k in range(members)])
+    return (lambda: [obj.download()]), (lambda s: obj.upload(s[0])), (lambda: [obj.jerk()]), [mass]
+
+
+def hermite(obj, dt, nsteps):
+    """nsteps fourth-order Hermite P(EC) steps of dt on a Context, an Ensemble or a Ragged, by host round trip over jerk():
+    the state is downloaded once at the start and a and adot taken there; per step the host predicts
+        xp = x + v dt + a dt^2/2 + adot dt^3/6,   vp = v + a dt + adot dt^2/2,
+    uploads the predicted state, calls jerk() for a1, adot1 there and corrects
+        v1 = v + (a + a1) dt/2 + (adot - adot1) dt^2/12,   x1 = x + (v + v1) dt/2 + (a - a1) dt^2/12
+    in fp64; a1 and adot1 start the next step (no second evaluation), and the corrected state is uploaded after the last step.
+    Cost: one upload and one read-back of O(n) per step, beside the jerk's pair work -- what a device-resident stepper would not
+    pay.  The masses are those given to this object's upload().  steps_done does not count these steps: it is what it was.  The
+    energies: as after any upload, the kinetic-energy partials belong to no state, so a step call of no steps reports 0 until a
+    step or a kick has run; diagnostics() sees the corrected state.  Returns the corrected state, the list of per-system dicts
+    uploaded last (fp64; one dict of (members, n) arrays for an ensemble); None where nsteps == 0."""
+    download, upload, jerk, mass = _hermite_io(obj)
+    if nsteps < 0:
+        raise NbxError(NBX_ERR_ARG, "hermite", "nsteps is negative")
+    if nsteps == 0:
+        return None
+    dt = float(dt)
+    pos, vel = FIELDS[:3], FIELDS[3:6]
+    acc, jrk = JERK_KEYS[:3], JERK_KEYS[3:]
+    st = [{f: np.asarray(s[f], dtype=np.float64) for f in FIELDS[:6]} for s in download()]
+    d0 = [{k: np.asarray(r[k], dtype=np.float64) for k in JERK_KEYS} for r in jerk()]
+    for step in range(nsteps):
+        pred = []
+        for s, d, m in zip(st, d0, mass):
+            p = {"mass": m}
+            for x, v, a, j in zip(pos, vel, acc, jrk):
+                p[x] = s[x] + dt * (s[v] + dt * (d[a] / 2.0 + dt * d[j] / 6.0))
+                p[v] = s[v] + dt * (d[a] + dt * d[j] / 2.0)
+            pred.append(p)
+        upload(pred)
+        d1 = [{k: np.asarray(r[k], dtype=np.float64) for k in JERK_KEYS} for r in jerk()]
+        new = []
+        for s, d, e in zip(st, d0, d1):
+            c = {}
+            for x, v, a, j in zip(pos, vel, acc, jrk):
+                c[v] = s[v] + dt * ((d[a] + e[a]) / 2.0 + dt * (d[j] - e[j]) / 12.0)
+                c[x] = s[x] + dt * ((s[v] + c[v]) / 2.0 + dt * (d[a] - e[a]) / 12.0)
+            new.append(c)
+        st, d0 = new, d1
+    upload([dict(s, mass=m) for s, m in zip(st, mass)])
+    return st
+
+
 def fof_catalogue(label, mass, x, y, z, min_members=2):
     """The groups of one system from fof()'s label and the bodies' masses and positions, in fp64: for every group of at least
     `min_members` bodies its label, members, mass and centre of mass, as {"label": (g,) int64, "members": (g,) int64, "mass":
@@ -822,6 +919,7 @@ class Context(_Handle, _Leapfrog, _Adaptive, _Tracers):
     def upload(self, state):
         arrs = [self._arr(state[f]) for f in FIELDS]
         _check(self._L.nbx_upload(self._h, *[_ptr(a) for a in arrs]), "nbx_upload")
+        _remember_mass(self, 0, [arrs[6]])
 
     def step(self, nsteps, dt=DT, kenergy=True):
         ke = ctypes.c_double(0.0)
@@ -898,6 +996,15 @@ class Context(_Handle, _Leapfrog, _Adaptive, _Tracers):
         lab = _clumps_label(label, (self.n,))
         out, a = _clumps_arrays((self.n,), self.dtype)
         _check(self._L.nbx_clumps(self._h, _ptr(lab), ctypes.byref(a)), "nbx_clumps")
+        return out
+
+    def jerk(self):
+        """nbx_jerk: the acceleration of every body and its time derivative at the current positions and velocities, as the six
+        JERK_KEYS arrays of n; acc is bit for bit field()'s at the bodies' own positions.  A sliced context is refused.
+        Synchronises."""
+        _need(self._L, "nbx_jerk")
+        out, a = _jerk_arrays((self.n,), self.dtype)
+        _check(self._L.nbx_jerk(self._h, ctypes.byref(a)), "nbx_jerk")
         return out
 
     def tidal(self, px, py, pz):
@@ -1152,6 +1259,7 @@ class Ensemble(_Batch):
             if a.ndim != 2 or a.shape != (arrs[0].shape[0], self.n):
                 raise NbxError(NBX_ERR_ARG, "array", "expected shape (count, %d), got %r" % (self.n, a.shape))
         self._call("upload", first, arrs[0].shape[0], *[_ptr(a) for a in arrs])
+        _remember_mass(self, first, arrs[6])
 
     def download(self, first=0, count=None):
         count = self.members - first if count is None else count
@@ -1208,6 +1316,16 @@ class Ensemble(_Batch):
         lab = _clumps_label(label, (max(count, 0), self.n))
         out, a = _clumps_arrays((max(count, 0), self.n), self.dtype)
         self._call("clumps", first, count, _ptr(lab), ctypes.byref(a))
+        return out
+
+    def jerk(self, first=0, count=None):
+        """nbx_ensemble_jerk: the six JERK_KEYS arrays (count, n) of members [first, first + count) (default: all from `first`)
+        -- for each member the bits Context.jerk() returns for a context of n bodies holding its state; one launch for all of
+        them.  Synchronises."""
+        _need(self._L, "nbx_ensemble_jerk")
+        count = self.members - first if count is None else count
+        out, a = _jerk_arrays((max(count, 0), self.n), self.dtype)
+        self._call("jerk", first, count, ctypes.byref(a))
         return out
 
     def binaries(self, bound=True, first=0, count=None):
@@ -1280,6 +1398,7 @@ class Ragged(_Batch):
         arrs = [np.ascontiguousarray(np.concatenate([np.asarray(s[f], dtype=self.dtype) for s in states]) if states
                                      else np.zeros(0, dtype=self.dtype)) for f in FIELDS]
         self._call("upload", first, len(states), *[_ptr(a) for a in arrs])
+        _remember_mass(self, first, [s["mass"] for s in states])
 
     def download(self, first=0, count=None):
         """Members [first, first + count) (default: all from `first`): a list of dicts of six arrays, one per member."""
@@ -1353,6 +1472,18 @@ class Ragged(_Batch):
         self._call("clumps", first, count, _ptr(lab), ctypes.byref(a))
         at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
         return [{k: flat[k][at[m]:at[m + 1]].copy() for k in CLUMPS_KEYS} for m in range(len(sizes))]
+
+    def jerk(self, first=0, count=None):
+        """nbx_ragged_jerk: one dict of the six JERK_KEYS arrays of sizes[k] per member of [first, first + count) (default: all
+        from `first`) -- the bits Context.jerk() returns for a context of sizes[k] bodies holding that member's state; one launch
+        for all of them.  Synchronises."""
+        _need(self._L, "nbx_ragged_jerk")
+        count = self.members - first if count is None else count
+        sizes = self._range(first, count)
+        flat, a = _jerk_arrays((max(sum(sizes), 1),), self.dtype)  # >= 1: an address is wanted, also for an empty range
+        self._call("jerk", first, count, ctypes.byref(a))
+        at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+        return [{k: flat[k][at[m]:at[m + 1]].copy() for k in JERK_KEYS} for m in range(len(sizes))]
 
     def binaries(self, bound=True, first=0, count=None):
         """nbx_ragged_binaries: one {"partner", "energy", "bound"} per member of [first, first + count) (default: all from
