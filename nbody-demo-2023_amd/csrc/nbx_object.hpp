@@ -158,6 +158,18 @@ struct Object {
   void* jerk_out = nullptr;
   void* jerk_tab = nullptr;
   size_t jerk_part_cap = 0, jerk_out_cap = 0;
+  // resident Hermite stepper (nbx_hermite.hip): the partial rows (two records per body and split) and the kept {a, 0}, {j, 0}
+  // records (two per velocity record), allocated on first use and of a size that is fixed for the object's life; herm_tab: a
+  // ragged ensemble's {pos_off, vel_off, out_off, n} per member, built on first use, herm_tab_src the host bytes its copy reads
+  // (no call of the stepper synchronises, so they live with the object); herm_have: a call has left kept records, made when
+  // steps_done was herm_steps and the current position buffer herm_cur -- what `resume` is checked against
+  void* herm_part = nullptr;
+  void* herm_keep = nullptr;
+  void* herm_tab = nullptr;
+  std::vector<char> herm_tab_src;
+  bool herm_have = false;
+  long long herm_steps = 0;
+  int herm_cur = 0;
   // resident tracers (nbx_tracers.hip): tr_m per system (0: none), every system's {x, y, z, 0} position and velocity records
   // one system after the other, and the partial rows of the pair work ([systems][tr_rows][tr_m] records, buffers of their own:
   // not the field's scratch), allocated by the first upload and grown likewise (sizes in bytes); tr_have: per system, its
@@ -372,7 +384,7 @@ inline void batch_release(Object* o) {
                   o->pc_out, o->pc_tab, o->knn_part, o->knn_out, o->knn_tab, o->fof_rec, o->fof_part,
                   o->fof_work, o->fof_out, o->fof_tab, o->bin_part, o->bin_out, o->bin_tab, o->tidal_pts, o->tidal_part,
                   o->tidal_out, o->tidal_tab, o->clump_lab, o->clump_part, o->clump_out, o->clump_tab, o->nl_seg, o->nl_scan, o->nl_index,
-                  o->nl_r2, o->nl_tab, o->jerk_part, o->jerk_out, o->jerk_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
+                  o->nl_r2, o->nl_tab, o->jerk_part, o->jerk_out, o->jerk_tab, o->herm_part, o->herm_keep, o->herm_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
     if (p) (void)hipFree(p);
   if (o->own_stream) (void)hipStreamDestroy(o->stream);
 }

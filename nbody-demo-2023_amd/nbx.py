@@ -111,6 +111,8 @@ GRAV = float(np.float32(6.67259e-11))  # the library's G: (float)6.67259e-11f, w
 # the symbols of include/nbx_jerk.h (the acceleration of every body and its time derivative), kept apart likewise
 JERK_SYMBOLS = ("nbx_jerk", "nbx_ensemble_jerk", "nbx_ragged_jerk")
 JERK_KEYS = ("acc_x", "acc_y", "acc_z", "jerk_x", "jerk_y", "jerk_z")
+# the symbols of include/nbx_hermite.h (the device-resident fourth-order Hermite stepper), kept apart likewise
+HERMITE_SYMBOLS = ("nbx_hermite_step", "nbx_ensemble_hermite_step", "nbx_ragged_hermite_step")
 
 
 class NbxError(RuntimeError):
@@ -365,6 +367,9 @@ def load():
         L.nbx_jerk.argtypes = [vp, ctypes.POINTER(JerkOut)]
         L.nbx_ensemble_jerk.argtypes = [vp, i32, i32, ctypes.POINTER(JerkOut)]
         L.nbx_ragged_jerk.argtypes = [vp, i32, i32, ctypes.POINTER(JerkOut)]
+    if hasattr(L, "nbx_hermite_step"):  # likewise for nbx_hermite.hip
+        for name in HERMITE_SYMBOLS:
+            getattr(L, name).argtypes = [vp, dbl, i32, i32]
     _lib = L
     return L
 
@@ -663,6 +668,7 @@ def jerk_dt(result, eta):
 def _remember_mass(obj, first, masses):
     """upload() keeps the masses it was given, per member: the library returns positions and velocities only, and hermite()
     uploads states of its own."""
+    obj._hermite_stale = True  # what a Hermite call kept belongs to the state before this upload (hermite_step, resume)
     if not hasattr(obj, "_mass"):
         obj._mass = {}
     for k, m in enumerate(masses):
@@ -872,6 +878,27 @@ class _Tracers:
         return self.kick(0.5 * dt, kenergy)
 
 
+class _Hermite:
+    """hermite_step() over the C-ABI call a class names in _hermite (include/nbx_hermite.h)."""
+
+    def hermite_step(self, dt, nsteps=1, resume=False):
+        """<prefix>_hermite_step: nsteps fourth-order Hermite P(EC) steps of dt of every body (of every member of a batch object)
+        on the device -- hermite()'s scheme without its round trip: two launches a step, nothing read back, no synchronisation.
+        resume=False evaluates the acceleration and its time derivative at the resident state first (two more launches);
+        resume=True continues from what the previous hermite_step() on this object kept, so that (dt, a) then (dt, b, resume=True)
+        is (dt, a + b) bit for bit -- the caller promises that no upload, step, kick, commit or local step came between (analysis
+        calls may).  The library refuses (NBX_ERR_STATE) what it sees of a broken promise -- no previous call, a step, a kick --
+        and this object refuses an upload made through it, which the library cannot see.  steps_done does not count these steps,
+        tracers do not move, and as after an upload a step call of no steps reports 0 until a step or a kick has run."""
+        _need(self._L, self._hermite)
+        if resume and getattr(self, "_hermite_stale", False) and getattr(self, "_hermite_kept", False):
+            raise NbxError(NBX_ERR_STATE, self._hermite, "%s: resume after an upload (what the previous Hermite call kept belongs to "
+                           "the state before it)" % self._hermite)
+        _check(getattr(self._L, self._hermite)(self._h, dt, nsteps, 1 if resume else 0), self._hermite)
+        if nsteps > 0:
+            self._hermite_stale, self._hermite_kept = False, True
+
+
 def suggest_dt(ts, eta):
     """eta / sqrt(rate) with rate the largest approach_rate2 or freefall_rate2 of `ts` -- one dict of timescale() or a list of
     them (the members of a batch object: the step all of them can take) -- or inf where every rate is 0."""
@@ -898,9 +925,10 @@ class _Adaptive:
         return t, len(dts), dts
 
 
-class Context(_Handle, _Leapfrog, _Adaptive, _Tracers):
+class Context(_Handle, _Leapfrog, _Adaptive, _Tracers, _Hermite):
     """One nbx_ctx.  Keyword options are the nbx_opts fields."""
     _destroy = "nbx_destroy"
+    _hermite = "nbx_hermite_step"
 
     def __init__(self, n, precision=32, **opts):
         self._new_handle()
@@ -1112,13 +1140,14 @@ class Context(_Handle, _Leapfrog, _Adaptive, _Tracers):
         return d.asdict()
 
 
-class _Batch(_Handle, _Leapfrog, _Adaptive, _Tracers):
+class _Batch(_Handle, _Leapfrog, _Adaptive, _Tracers, _Hermite):
     """What Ensemble and Ragged share -- the library serves both from one host layer (csrc/nbx_batch.hpp), and every method here
     is the C-ABI call of that name under the class's prefix.  A subclass sets members and precision, calls _create, and adds
     upload and download, which differ in how the members' arrays are laid out."""
     _prefix = None   # "nbx_ensemble": <prefix>_create, <prefix>_step, ...
     _stats = None    # the ctypes mirror of <prefix>_stats_t
     _what = None     # the entry points, as the "was built without ..." error names them
+    _hermite = property(lambda self: self._prefix + "_hermite_step")
 
     def _call(self, name, *args):
         where = "%s_%s" % (self._prefix, name)
