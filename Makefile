@@ -53,9 +53,11 @@ $(PKG)/nbx_jerk.o: $(CSRC)/nbx_jerk.hip $(CSRC)/nbx_jerk_kernels.hpp $(CSRC)/nbx
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(PKG)/nbx_hermite.o: $(CSRC)/nbx_hermite.hip $(CSRC)/nbx_hermite_kernels.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_hermite.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(PKG)/nbx_advance.o: $(CSRC)/nbx_advance.hip $(CSRC)/nbx_advance_kernels.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_advance.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(PKG)/nbx_ic.o: $(CSRC)/nbx_ic.cpp include/nbx.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -Wall -ffp-contract=off -c $< -o $@
-$(PKG)/libnbx.so: $(PKG)/nbx_api.o $(PKG)/nbx_group.o $(PKG)/nbx_diag.o $(PKG)/nbx_ensemble.o $(PKG)/nbx_ensemble_diag.o $(PKG)/nbx_ragged.o $(PKG)/nbx_ragged_diag.o $(PKG)/nbx_batch_accel.o $(PKG)/nbx_kick.o $(PKG)/nbx_timescale.o $(PKG)/nbx_field.o $(PKG)/nbx_neighbours.o $(PKG)/nbx_paircount.o $(PKG)/nbx_tracers.o $(PKG)/nbx_knn.o $(PKG)/nbx_fof.o $(PKG)/nbx_binaries.o $(PKG)/nbx_tidal.o $(PKG)/nbx_clumps.o $(PKG)/nbx_nlist.o $(PKG)/nbx_jerk.o $(PKG)/nbx_hermite.o $(PKG)/nbx_ic.o
+$(PKG)/libnbx.so: $(PKG)/nbx_api.o $(PKG)/nbx_group.o $(PKG)/nbx_diag.o $(PKG)/nbx_ensemble.o $(PKG)/nbx_ensemble_diag.o $(PKG)/nbx_ragged.o $(PKG)/nbx_ragged_diag.o $(PKG)/nbx_batch_accel.o $(PKG)/nbx_kick.o $(PKG)/nbx_timescale.o $(PKG)/nbx_field.o $(PKG)/nbx_neighbours.o $(PKG)/nbx_paircount.o $(PKG)/nbx_tracers.o $(PKG)/nbx_knn.o $(PKG)/nbx_fof.o $(PKG)/nbx_binaries.o $(PKG)/nbx_tidal.o $(PKG)/nbx_clumps.o $(PKG)/nbx_nlist.o $(PKG)/nbx_jerk.o $(PKG)/nbx_hermite.o $(PKG)/nbx_advance.o $(PKG)/nbx_ic.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -ldl
 
 host: lib

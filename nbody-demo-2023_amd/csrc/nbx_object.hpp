@@ -170,6 +170,19 @@ struct Object {
   bool herm_have = false;
   long long herm_steps = 0;
   int herm_cur = 0;
+  // adaptive power-of-two steps (nbx_advance.hip): it works in herm_part, herm_keep and herm_tab (the same sizes and layout) and
+  // adds the candidates, one double per body, and the clock records, one per system, allocated on first use and of a size that
+  // is fixed for the object's life; adv_have: an advance call has left clocks and kept records, made when steps_done was
+  // adv_steps and the current position buffer adv_cur, with these dt_cap and levels -- what its `resume` is checked against --
+  // and this t_end, which the clock calls report `done` against
+  void* adv_cand = nullptr;
+  void* adv_clock = nullptr;
+  bool adv_have = false;
+  long long adv_steps = 0;
+  int adv_cur = 0;
+  int adv_levels = 0;
+  double adv_dt_cap = 0.0;
+  double adv_t_end = 0.0;
   // resident tracers (nbx_tracers.hip): tr_m per system (0: none), every system's {x, y, z, 0} position and velocity records
   // one system after the other, and the partial rows of the pair work ([systems][tr_rows][tr_m] records, buffers of their own:
   // not the field's scratch), allocated by the first upload and grown likewise (sizes in bytes); tr_have: per system, its
@@ -384,7 +397,7 @@ inline void batch_release(Object* o) {
                   o->pc_out, o->pc_tab, o->knn_part, o->knn_out, o->knn_tab, o->fof_rec, o->fof_part,
                   o->fof_work, o->fof_out, o->fof_tab, o->bin_part, o->bin_out, o->bin_tab, o->tidal_pts, o->tidal_part,
                   o->tidal_out, o->tidal_tab, o->clump_lab, o->clump_part, o->clump_out, o->clump_tab, o->nl_seg, o->nl_scan, o->nl_index,
-                  o->nl_r2, o->nl_tab, o->jerk_part, o->jerk_out, o->jerk_tab, o->herm_part, o->herm_keep, o->herm_tab, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
+                  o->nl_r2, o->nl_tab, o->jerk_part, o->jerk_out, o->jerk_tab, o->herm_part, o->herm_keep, o->herm_tab, o->adv_cand, o->adv_clock, o->tr_pos, o->tr_vel, o->tr_part, o->tr_tab})
     if (p) (void)hipFree(p);
   if (o->own_stream) (void)hipStreamDestroy(o->stream);
 }

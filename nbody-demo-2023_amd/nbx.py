@@ -113,6 +113,8 @@ JERK_SYMBOLS = ("nbx_jerk", "nbx_ensemble_jerk", "nbx_ragged_jerk")
 JERK_KEYS = ("acc_x", "acc_y", "acc_z", "jerk_x", "jerk_y", "jerk_z")
 # the symbols of include/nbx_hermite.h (the device-resident fourth-order Hermite stepper), kept apart likewise
 HERMITE_SYMBOLS = ("nbx_hermite_step", "nbx_ensemble_hermite_step", "nbx_ragged_hermite_step")
+# the symbols of include/nbx_advance.h (adaptive power-of-two time steps chosen on the device), kept apart likewise
+ADVANCE_SYMBOLS = ("nbx_advance", "nbx_ensemble_advance", "nbx_ragged_advance", "nbx_clock", "nbx_ensemble_clock", "nbx_ragged_clock")
 
 
 class NbxError(RuntimeError):
@@ -174,6 +176,20 @@ class Timescale(ctypes.Structure):
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+class Clock(ctypes.Structure):
+    """nbx_clock_t (include/nbx_advance.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("n", ctypes.c_int32), ("t", ctypes.c_double), ("dt_last", ctypes.c_double),
+        ("dt_next", ctypes.c_double), ("steps", ctypes.c_int64), ("floor_steps", ctypes.c_int64), ("done", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+    def asdict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("struct_size", "reserved")}
+        d["done"] = bool(d["done"])
+        return d
 
 
 class ClumpsOut(ctypes.Structure):
@@ -370,6 +386,12 @@ def load():
     if hasattr(L, "nbx_hermite_step"):  # likewise for nbx_hermite.hip
         for name in HERMITE_SYMBOLS:
             getattr(L, name).argtypes = [vp, dbl, i32, i32]
+    if hasattr(L, "nbx_advance"):  # likewise for nbx_advance.hip
+        for name in ADVANCE_SYMBOLS[:3]:
+            getattr(L, name).argtypes = [vp, dbl, dbl, i32, dbl, i32, i32]
+        L.nbx_clock.argtypes = [vp, ctypes.POINTER(Clock)]
+        L.nbx_ensemble_clock.argtypes = [vp, i32, i32, ctypes.POINTER(Clock)]
+        L.nbx_ragged_clock.argtypes = [vp, i32, i32, ctypes.POINTER(Clock)]
     _lib = L
     return L
 
@@ -669,6 +691,7 @@ def _remember_mass(obj, first, masses):
     """upload() keeps the masses it was given, per member: the library returns positions and velocities only, and hermite()
     uploads states of its own."""
     obj._hermite_stale = True  # what a Hermite call kept belongs to the state before this upload (hermite_step, resume)
+    obj._advance_stale = True  # and so do the clocks and the kept records of an advance call (advance, resume)
     if not hasattr(obj, "_mass"):
         obj._mass = {}
     for k, m in enumerate(masses):
@@ -899,6 +922,48 @@ class _Hermite:
             self._hermite_stale, self._hermite_kept = False, True
 
 
+class _Advance:
+    """advance() and clock() over the C-ABI calls a class names in _advance and _clock (include/nbx_advance.h)."""
+
+    def advance(self, t_end, dt_cap, eta=0.125, levels=20, max_steps=32, resume=False):
+        """<prefix>_advance: up to max_steps fourth-order Hermite P(EC) steps of every system -- the context, or each member of a
+        batch object -- towards t_end, every system with a clock of its own and a step it chooses itself on the device: a power
+        of two in [dt_cap * 2**-levels, dt_cap], eta * sqrt(q) rounded down, q the smallest of the bodies' step criteria.  dt_cap
+        is a power of two and t_end a whole multiple of it, so every system lands on t_end exactly and then stops.  Three launches
+        a step, nothing read back, no synchronisation: call advance(max_steps = a few dozen), then clock(), until every system
+        is done.  resume=False starts the clocks at t = 0 and evaluates at the resident state first (also with max_steps=0, so
+        that clock()["dt_next"] can be asked for before the first step); resume=True continues -- the caller promises that no
+        upload, step, kick, commit, local step or hermite_step() came between (analysis calls may); dt_cap and levels must be
+        the previous call's, eta may change, t_end may grow.  The library refuses (NBX_ERR_STATE) what it sees of a broken
+        promise, and this object refuses an upload made through it.  A step of size h leaves the bits hermite_step(h) leaves;
+        steps_done does not count these steps and tracers do not move."""
+        _need(self._L, self._advance)
+        if resume and getattr(self, "_advance_stale", False) and getattr(self, "_advance_kept", False):
+            raise NbxError(NBX_ERR_STATE, self._advance, "%s: resume after an upload (the clocks and what the previous advance call "
+                           "kept belong to the state before it)" % self._advance)
+        _check(getattr(self._L, self._advance)(self._h, t_end, dt_cap, levels, eta, max_steps, 1 if resume else 0), self._advance)
+        if not resume:
+            self._advance_stale, self._advance_kept = False, True
+
+    def clock(self, first=0, count=None):
+        """<prefix>_clock: {"n", "t", "dt_last", "dt_next", "steps", "floor_steps", "done"} of the context, or one such dict per
+        member of [first, first + count) of a batch object (default: all from `first`).  Synchronises once."""
+        _need(self._L, self._clock)
+        if not hasattr(self, "members"):
+            if first != 0 or count is not None:
+                raise NbxError(NBX_ERR_ARG, self._clock, "a context has one clock: no member range")
+            c = Clock()
+            c.struct_size = ctypes.sizeof(Clock)
+            _check(getattr(self._L, self._clock)(self._h, ctypes.byref(c)), self._clock)
+            return c.asdict()
+        count = self.members - first if count is None else count
+        c = (Clock * max(count, 1))()
+        for k in range(max(count, 0)):
+            c[k].struct_size = ctypes.sizeof(Clock)
+        _check(getattr(self._L, self._clock)(self._h, first, count, c), self._clock)
+        return [c[k].asdict() for k in range(max(count, 0))]
+
+
 def suggest_dt(ts, eta):
     """eta / sqrt(rate) with rate the largest approach_rate2 or freefall_rate2 of `ts` -- one dict of timescale() or a list of
     them (the members of a batch object: the step all of them can take) -- or inf where every rate is 0."""
@@ -925,10 +990,12 @@ class _Adaptive:
         return t, len(dts), dts
 
 
-class Context(_Handle, _Leapfrog, _Adaptive, _Tracers, _Hermite):
+class Context(_Handle, _Leapfrog, _Adaptive, _Tracers, _Hermite, _Advance):
     """One nbx_ctx.  Keyword options are the nbx_opts fields."""
     _destroy = "nbx_destroy"
     _hermite = "nbx_hermite_step"
+    _advance = "nbx_advance"
+    _clock = "nbx_clock"
 
     def __init__(self, n, precision=32, **opts):
         self._new_handle()
@@ -1140,7 +1207,7 @@ class Context(_Handle, _Leapfrog, _Adaptive, _Tracers, _Hermite):
         return d.asdict()
 
 
-class _Batch(_Handle, _Leapfrog, _Adaptive, _Tracers, _Hermite):
+class _Batch(_Handle, _Leapfrog, _Adaptive, _Tracers, _Hermite, _Advance):
     """What Ensemble and Ragged share -- the library serves both from one host layer (csrc/nbx_batch.hpp), and every method here
     is the C-ABI call of that name under the class's prefix.  A subclass sets members and precision, calls _create, and adds
     upload and download, which differ in how the members' arrays are laid out."""
@@ -1148,6 +1215,8 @@ class _Batch(_Handle, _Leapfrog, _Adaptive, _Tracers, _Hermite):
     _stats = None    # the ctypes mirror of <prefix>_stats_t
     _what = None     # the entry points, as the "was built without ..." error names them
     _hermite = property(lambda self: self._prefix + "_hermite_step")
+    _advance = property(lambda self: self._prefix + "_advance")
+    _clock = property(lambda self: self._prefix + "_clock")
 
     def _call(self, name, *args):
         where = "%s_%s" % (self._prefix, name)

@@ -13,7 +13,7 @@ cp "$root"/include/nbx.h "$root"/include/nbx_diag.h "$root"/include/nbx_ensemble
    "$root"/include/nbx_timescale.h "$root"/include/nbx_field.h "$root"/include/nbx_neighbours.h \
    "$root"/include/nbx_paircount.h "$root"/include/nbx_tracers.h "$root"/include/nbx_knn.h "$root"/include/nbx_fof.h \
    "$root"/include/nbx_binaries.h "$root"/include/nbx_tidal.h "$root"/include/nbx_clumps.h "$root"/include/nbx_nlist.h \
-   "$root"/include/nbx_jerk.h "$root"/include/nbx_hermite.h "$dir/include/"
+   "$root"/include/nbx_jerk.h "$root"/include/nbx_hermite.h "$root"/include/nbx_advance.h "$dir/include/"
 env "$@" python3 "$here/gen_sgpr_loop.py" "$dir/pkg/csrc/nbx_sgpr_loop.inc"
 flags="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -fhip-fp32-correctly-rounded-divide-sqrt"
 # csrc includes "../../include/nbx_diag.h" (which includes nbx.h) relative to pkg/csrc -> $dir/include
@@ -35,6 +35,7 @@ flags="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -fh
  hipcc $flags -c nbx_nlist.hip -o ../nbx_nlist.o &&
  hipcc $flags -c nbx_jerk.hip -o ../nbx_jerk.o &&
  hipcc $flags -c nbx_hermite.hip -o ../nbx_hermite.o &&
+ hipcc $flags -c nbx_advance.hip -o ../nbx_advance.o &&
  hipcc -O2 -std=c++17 -fPIC -ffp-contract=off -c nbx_ic.cpp -o ../nbx_ic.o)
 hipcc --offload-arch=gfx950 -shared -fPIC -o "$dir/libnbx.so" "$dir"/pkg/*.o -ldl
 echo "built $dir/libnbx.so"
