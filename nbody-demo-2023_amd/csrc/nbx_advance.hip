@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/nbx_advance.h"
+#include "nbx_analysis.hpp"           // object_bodies, bodies_noun, ragged_member_table, ragged_extents
 #include "nbx_advance_kernels.hpp"
 #include "nbx_ensemble_internal.hpp"  // struct nbx_ensemble; nbx_batch.hpp: check_range, check_uploaded
 #include "nbx_internal.hpp"           // struct nbx_ctx
@@ -197,37 +198,19 @@ int advance_t(nbx_ensemble* e, const char* where, const AdvancePlan& p) {
 template <typename T>
 int advance_t(nbx_ragged* r, const char* where, const AdvancePlan& p) {
   using T4 = typename V4<T>::type;
-  if (!r->herm_tab) {
-    std::vector<AdvanceMember> table((size_t)r->members);
-    unsigned long long off = 0;
-    for (int k = 0; k < r->members; ++k) {
-      const MemberSpan mem = r->layout(k);
-      table[(size_t)k] = AdvanceMember{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, off, mem.n, 0};
-      off += (unsigned long long)mem.n;
-    }
-    r->herm_tab_src.resize(sizeof(AdvanceMember) * table.size());  // the copy's source lives with the object: nothing here waits for it
-    std::memcpy(r->herm_tab_src.data(), table.data(), r->herm_tab_src.size());
-    char* dev = nullptr;
-    const int rc = device_table(r, &dev, r->herm_tab_src, where, "the member table");
-    if (rc) return rc;
-    r->herm_tab = dev;
-  }
-  int columns = 1, row_splits = 1;
-  size_t total = 0;
-  for (int k = 0; k < r->members; ++k) {
-    const int n = r->layout(k).n;
-    const FieldShape s = field_shape(n, n);
-    columns = std::max(columns, s.columns);
-    row_splits = std::max(row_splits, s.splits);
-    total += (size_t)n;
-  }
+  // the copy's source, herm_tab_src, lives with the object: nothing here waits for it
+  const int rc = ragged_member_table<AdvanceMember>(r, &r->herm_tab, &r->herm_tab_src, where, [](const MemberSpan& mem, unsigned long long out_off) {
+    return AdvanceMember{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, out_off, mem.n, 0};
+  });
+  if (rc) return rc;
+  const GridExtents g = ragged_extents(r, 0, r->members);
   const AdvanceMember* dev = (const AdvanceMember*)r->herm_tab;
   AdvanceFinishArgs<T> fin{};
   fin.table = dev;
   fin.members = r->members;
   AdvanceClockArgs clk{};
   clk.table = dev;
-  return run_advance<T>(r, where, total, (size_t)r->members, row_splits, span_of(r, 0, r->members).vel_count, p, fin, clk, [&](const PairLaunch<T>& l) {
+  return run_advance<T>(r, where, (size_t)object_bodies(r), (size_t)r->members, g.splits, span_of(r, 0, r->members).vel_count, p, fin, clk, [&](const PairLaunch<T>& l) {
     RaggedAdvanceArgs<T> k{};
     k.posm = (const T4*)r->posm[r->cur];
     k.velm = (const T4*)r->velm;
@@ -236,20 +219,15 @@ int advance_t(nbx_ragged* r, const char* where, const AdvancePlan& p) {
     k.parts = l.parts;
     k.predict = l.predict;
     k.tm = l.tm;
-    hipLaunchKernelGGL(ragged_advance_kernel<T>, dim3(columns, row_splits, r->members), dim3(kBlock), 0, r->stream, k);
+    hipLaunchKernelGGL(ragged_advance_kernel<T>, dim3(g.columns, g.splits, r->members), dim3(kBlock), 0, r->stream, k);
   });
 }
 
+// a context's side of object_bodies and bodies_noun (nbx_analysis.hpp has the batch kinds'): check_arguments serves all three
+using nbx_detail::bodies_noun;
+using nbx_detail::object_bodies;
 long long object_bodies(const nbx_ctx* c) { return (long long)c->n; }
-long long object_bodies(const nbx_ensemble* e) { return (long long)e->members * e->n; }
-long long object_bodies(const nbx_ragged* r) {
-  long long total = 0;
-  for (int k = 0; k < r->members; ++k) total += r->layout(k).n;
-  return total;
-}
 const char* bodies_noun(const nbx_ctx*) { return "n exceeds"; }
-const char* bodies_noun(const nbx_ensemble*) { return "members * n exceeds"; }
-const char* bodies_noun(const nbx_ragged*) { return "the bodies of the members exceed"; }
 
 bool positive(double x) { return std::isfinite(x) && x > 0.0; }
 

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/nbx_binaries.h"
+#include "nbx_analysis.hpp"           // ensure_bytes, range_bodies, ragged_member_table, ragged_extents, read_back
 #include "nbx_binaries_kernels.hpp"
 #include "nbx_ensemble_internal.hpp"  // struct nbx_ensemble; nbx_batch.hpp: check_range, check_uploaded, device_table
 #include "nbx_internal.hpp"           // struct nbx_ctx
@@ -24,20 +25,6 @@ using namespace nbx;
 using namespace nbx_detail;
 
 namespace {
-
-// *p holds at least `bytes`: allocated on first use, replaced by a larger buffer -- never a smaller one -- when a call needs more
-int ensure_bytes(void** p, size_t* cap, size_t bytes, const char* where, const char* what) {
-  if (*p && *cap >= bytes) return NBX_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  char* dev = nullptr;
-  const int rc = device_alloc(&dev, bytes, where, what);
-  if (rc) return rc;
-  *p = dev;
-  *cap = bytes;
-  return NBX_OK;
-}
 
 struct Outputs {
   int32_t* partner;
@@ -58,20 +45,15 @@ int run_binaries(Object* o, const char* where, size_t total, int row_splits, con
   rc = ensure_bytes(&o->bin_out, &o->bin_out_cap, sizeof(Rec) * total, where, "the results");
   if (rc) return rc;
   std::vector<Rec> res(total);
-  const int rc_run = [&]() -> int {
+  rc = read_back(o, res.data(), o->bin_out, sizeof(Rec) * total, [&]() -> int {
     launch((Rec*)o->bin_part);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(bound_finish_kernel<T>, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, o->stream,
                        (const Rec*)o->bin_part, table, first, count, n_all, row_splits, (unsigned)total, (Rec*)o->bin_out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(res.data(), o->bin_out, sizeof(Rec) * total, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
     return NBX_OK;
-  }();
-  if (rc_run) {
-    (void)hipStreamSynchronize(o->stream);  // no copy may outlive `res`
-    return rc_run;
-  }
+  });
+  if (rc) return rc;
   T* energy = (T*)a.energy;
   for (size_t i = 0; i < total; ++i) {
     if (a.partner) a.partner[i] = res[i].j;
@@ -95,15 +77,6 @@ int binaries_ctx_t(nbx_ctx* c, const char* where, const Outputs& a) {
                          s.tiles_per_split, parts);
   });
 }
-
-long long range_bodies(const nbx_ensemble* e, int, int count) { return (long long)count * e->n; }
-long long range_bodies(const nbx_ragged* r, int first, int count) {
-  long long total = 0;
-  for (int k = first; k < first + count; ++k) total += r->layout(k).n;
-  return total;
-}
-const char* range_noun(const nbx_ensemble*) { return "count * n exceeds"; }
-const char* range_noun(const nbx_ragged*) { return "the bodies of the range exceed"; }
 
 template <typename T>
 int binaries_members_t(nbx_ensemble* e, const char* where, int first, int count, const Outputs& a) {
@@ -131,35 +104,20 @@ template <typename T>
 int binaries_members_t(nbx_ragged* r, const char* where, int first, int count, const Outputs& a) {
   using T4 = typename V4<T>::type;
   std::vector<BoundMember> table;  // lives until run_binaries has synchronised
-  if (!r->bin_tab) {
-    table.resize((size_t)r->members);
-    unsigned long long off = 0;
-    for (int k = 0; k < r->members; ++k) {
-      const MemberSpan mem = r->layout(k);
-      table[(size_t)k] = BoundMember{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, off, mem.n, 0};
-      off += (unsigned long long)mem.n;
-    }
-    BoundMember* dev = nullptr;
-    const int rc = device_table(r, &dev, table, where, "the member table");
-    if (rc) return rc;
-    r->bin_tab = dev;
-  }
-  int columns = 1, row_splits = 1;
-  for (int k = first; k < first + count; ++k) {
-    const int n = r->layout(k).n;
-    const FieldShape s = field_shape(n, n);
-    columns = std::max(columns, s.columns);
-    row_splits = std::max(row_splits, s.splits);
-  }
+  const int rc = ragged_member_table<BoundMember>(r, &r->bin_tab, &table, where, [](const MemberSpan& mem, unsigned long long out_off) {
+    return BoundMember{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, out_off, mem.n, 0};
+  });
+  if (rc) return rc;
+  const GridExtents g = ragged_extents(r, first, count);
   const BoundMember* dev = (const BoundMember*)r->bin_tab;
-  return run_binaries<T>(r, where, (size_t)range_bodies(r, first, count), row_splits, dev, (unsigned)first, count, 0, a, [&](BoundRecord<T>* parts) {
+  return run_binaries<T>(r, where, (size_t)range_bodies(r, first, count), g.splits, dev, (unsigned)first, count, 0, a, [&](BoundRecord<T>* parts) {
     RaggedBoundArgs<T> k{};
     k.posm = (const T4*)r->posm[r->cur];
     k.velm = (const T4*)r->velm;
     k.table = dev;
     k.parts = parts;
     k.first = (unsigned)first;
-    const dim3 grid(columns, row_splits, count);
+    const dim3 grid(g.columns, g.splits, count);
     if (a.bound) hipLaunchKernelGGL((ragged_bound_kernel<T, true>), grid, dim3(kBlock), 0, r->stream, k);
     else hipLaunchKernelGGL((ragged_bound_kernel<T, false>), grid, dim3(kBlock), 0, r->stream, k);
   });

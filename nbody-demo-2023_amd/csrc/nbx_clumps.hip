@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/nbx_clumps.h"
+#include "nbx_analysis.hpp"           // ensure_bytes, range_bodies, ragged_member_table, ragged_extents, read_back
 #include "nbx_clumps_kernels.hpp"
 #include "nbx_ensemble_internal.hpp"  // struct nbx_ensemble; nbx_batch.hpp: check_range, check_uploaded, device_table
 #include "nbx_internal.hpp"           // struct nbx_ctx
@@ -24,20 +25,6 @@ using namespace nbx;
 using namespace nbx_detail;
 
 namespace {
-
-// *p holds at least `bytes`: allocated on first use, replaced by a larger buffer -- never a smaller one -- when a call needs more
-int ensure_bytes(void** p, size_t* cap, size_t bytes, const char* where, const char* what) {
-  if (*p && *cap >= bytes) return NBX_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  char* dev = nullptr;
-  const int rc = device_alloc(&dev, bytes, where, what);
-  if (rc) return rc;
-  *p = dev;
-  *cap = bytes;
-  return NBX_OK;
-}
 
 bool no_output(const nbx_clumps_out_t& a) {
   return !a.members && !a.gm && !a.centre[0] && !a.centre[1] && !a.centre[2] && !a.velocity[0] && !a.velocity[1] && !a.velocity[2] &&
@@ -76,14 +63,14 @@ int run_clumps(Object* o, const char* where, size_t total, int row_splits, const
   using T4 = typename V4<T>::type;
   const size_t rows = total * (size_t)row_splits;
   const size_t out_bytes = (sizeof(T4) * kClumpOutRecords + sizeof(int)) * total;
-  const int rc = reserve_clumps<T>(o, where, total, row_splits);  // a ragged ensemble has them already: nothing happens
+  int rc = reserve_clumps<T>(o, where, total, row_splits);  // a ragged ensemble has them already: nothing happens
   if (rc) return rc;
   T4* parts = (T4*)o->clump_part;
   int* counts = (int*)(parts + 2 * rows);
   T4* out = (T4*)o->clump_out;
   int* members = (int*)(out + (size_t)kClumpOutRecords * total);
   std::vector<char> host(out_bytes);
-  const int rc_run = [&]() -> int {
+  rc = read_back(o, host.data(), o->clump_out, out_bytes, [&]() -> int {
     HIP_TRY(hipMemcpyAsync(o->clump_lab, label, sizeof(int) * total, hipMemcpyHostToDevice, o->stream));
     launch((const int*)o->clump_lab, parts, counts);
     HIP_TRY(hipGetLastError());
@@ -105,14 +92,9 @@ int run_clumps(Object* o, const char* where, size_t total, int row_splits, const
     f.members = members;
     hipLaunchKernelGGL(clump_finish_kernel<T>, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, o->stream, f);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(host.data(), o->clump_out, out_bytes, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
     return NBX_OK;
-  }();
-  if (rc_run) {
-    (void)hipStreamSynchronize(o->stream);  // no copy may outlive `host` or still read `label`
-    return rc_run;
-  }
+  });
+  if (rc) return rc;  // read_back has synchronised: no copy outlives `host` or still reads `label`
   const T* rec = (const T*)host.data();  // 12 values of T per body
   const int* mem = (const int*)(host.data() + sizeof(T4) * kClumpOutRecords * total);
   T* dst[9] = {(T*)a.gm, (T*)a.centre[0], (T*)a.centre[1], (T*)a.centre[2], (T*)a.velocity[0], (T*)a.velocity[1], (T*)a.velocity[2],
@@ -135,15 +117,6 @@ int clumps_ctx_t(nbx_ctx* c, const char* where, const int32_t* label, const nbx_
                        s.tiles_per_split, parts, counts);
   });
 }
-
-long long range_bodies(const nbx_ensemble* e, int, int count) { return (long long)count * e->n; }
-long long range_bodies(const nbx_ragged* r, int first, int count) {
-  long long total = 0;
-  for (int k = first; k < first + count; ++k) total += r->layout(k).n;
-  return total;
-}
-const char* range_noun(const nbx_ensemble*) { return "count * n exceeds"; }
-const char* range_noun(const nbx_ragged*) { return "the bodies of the range exceed"; }
 
 template <typename T>
 int clumps_members_t(nbx_ensemble* e, const char* where, int first, int count, const int32_t* label, const nbx_clumps_out_t& a) {
@@ -172,17 +145,11 @@ int clumps_members_t(nbx_ensemble* e, const char* where, int first, int count, c
 template <typename T>
 int clumps_members_t(nbx_ragged* r, const char* where, int first, int count, const int32_t* label, const nbx_clumps_out_t& a) {
   using T4 = typename V4<T>::type;
-  int columns = 1, row_splits = 1;
-  for (int k = first; k < first + count; ++k) {
-    const int n = r->layout(k).n;
-    const FieldShape s = field_shape(n, n);
-    columns = std::max(columns, s.columns);
-    row_splits = std::max(row_splits, s.splits);
-  }
+  const GridExtents g = ragged_extents(r, first, count);
   const size_t total = (size_t)range_bodies(r, first, count);
   // every allocation of the call before the table's copy is enqueued: from there on every path ends in run_clumps'
   // synchronisation, which `table` outlives
-  int rc = reserve_clumps<T>(r, where, total, row_splits);
+  int rc = reserve_clumps<T>(r, where, total, g.splits);
   if (rc) return rc;
   std::vector<ClumpMember> table;
   // declared after `table`, so it runs first: if an exception (out of host memory) leaves this call while the table's copy is
@@ -192,22 +159,13 @@ int clumps_members_t(nbx_ragged* r, const char* where, int first, int count, con
     bool armed;
     ~Drain() { if (armed) (void)hipStreamSynchronize(stream); }
   } drain{r->stream, false};
-  if (!r->clump_tab) {
-    table.resize((size_t)r->members);
-    unsigned long long off = 0;
-    for (int k = 0; k < r->members; ++k) {
-      const MemberSpan mem = r->layout(k);
-      table[(size_t)k] = ClumpMember{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, off, mem.n, 0};
-      off += (unsigned long long)mem.n;
-    }
-    ClumpMember* dev = nullptr;
-    rc = device_table(r, &dev, table, where, "the member table");
-    if (rc) return rc;  // nothing was enqueued
-    r->clump_tab = dev;
-    drain.armed = true;
-  }
+  rc = ragged_member_table<ClumpMember>(r, &r->clump_tab, &table, where, [](const MemberSpan& mem, unsigned long long out_off) {
+    return ClumpMember{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, out_off, mem.n, 0};
+  });
+  if (rc) return rc;  // nothing was enqueued
+  drain.armed = !table.empty();  // this call has built the table: its copy is in flight
   const Resident<T> res{(const T4*)r->posm[r->cur], (const T4*)r->velm, (const ClumpMember*)r->clump_tab, (unsigned)first, count, 0, 0u, 0u};
-  rc = run_clumps<T>(r, where, total, row_splits, res, label, a, [&](const int* lab, T4* parts, int* counts) {
+  rc = run_clumps<T>(r, where, total, g.splits, res, label, a, [&](const int* lab, T4* parts, int* counts) {
     RaggedClumpArgs<T> k{};
     k.posm = res.posm;
     k.velm = res.velm;
@@ -216,7 +174,7 @@ int clumps_members_t(nbx_ragged* r, const char* where, int first, int count, con
     k.parts = parts;
     k.counts = counts;
     k.first = (unsigned)first;
-    hipLaunchKernelGGL(ragged_clump_kernel<T>, dim3(columns, row_splits, count), dim3(kBlock), 0, r->stream, k);
+    hipLaunchKernelGGL(ragged_clump_kernel<T>, dim3(g.columns, g.splits, count), dim3(kBlock), 0, r->stream, k);
   });
   drain.armed = false;  // run_clumps has synchronised on every path it returns by
   return rc;

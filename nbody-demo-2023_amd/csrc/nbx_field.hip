@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/nbx_field.h"
+#include "nbx_analysis.hpp"           // ensure_bytes, ragged_member_table, ragged_extents, read_back
 #include "nbx_ensemble_internal.hpp"  // struct nbx_ensemble; nbx_batch.hpp: check_range, check_uploaded
 #include "nbx_field_kernels.hpp"
 #include "nbx_internal.hpp"         // struct nbx_ctx
@@ -24,20 +25,6 @@ using namespace nbx;
 using namespace nbx_detail;
 
 namespace {
-
-// *p holds at least `bytes`: allocated on first use, replaced by a larger buffer -- never a smaller one -- when a call needs more
-int ensure_bytes(void** p, size_t* cap, size_t bytes, const char* where, const char* what) {
-  if (*p && *cap >= bytes) return NBX_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  char* dev = nullptr;
-  const int rc = device_alloc(&dev, bytes, where, what);
-  if (rc) return rc;
-  *p = dev;
-  *cap = bytes;
-  return NBX_OK;
-}
 
 struct Arrays {
   const void *px, *py, *pz;
@@ -65,21 +52,16 @@ int run_field(Object* o, const char* where, int count, int m, int row_splits, co
     host[i] = q;
   }
   std::vector<T4> res(total);  // not `host`: the points may still be leaving it
-  const int rc_run = [&]() -> int {
+  rc = read_back(o, res.data(), o->field_out, sizeof(T4) * total, [&]() -> int {
     HIP_TRY(hipMemcpyAsync(o->field_pts, host.data(), sizeof(T4) * total, hipMemcpyHostToDevice, o->stream));
     launch((const T4*)o->field_pts, (T4*)o->field_part);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(field_finish_kernel<T>, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, o->stream,
                        (const T4*)o->field_part, table, first, n_all, m, row_splits, (unsigned)total, (T4*)o->field_out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(res.data(), o->field_out, sizeof(T4) * total, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
     return NBX_OK;
-  }();
-  if (rc_run) {
-    (void)hipStreamSynchronize(o->stream);  // no copy may outlive `host` and `res`
-    return rc_run;
-  }
+  });
+  if (rc) return rc;  // read_back has synchronised: no copy outlives `host` and `res`
   T *ax = (T*)a.ax, *ay = (T*)a.ay, *az = (T*)a.az, *phi = (T*)a.phi;
   for (size_t i = 0; i < total; ++i) {
     if (ax) ax[i] = res[i].x;
@@ -124,25 +106,13 @@ template <typename T>
 int field_members_t(nbx_ragged* r, const char* where, int first, int count, int m, const Arrays& a) {
   using T4 = typename V4<T>::type;
   std::vector<FieldMember> table;  // lives until run_field has synchronised
-  if (!r->field_tab) {
-    table.resize((size_t)r->members);
-    for (int k = 0; k < r->members; ++k) {
-      const MemberSpan mem = r->layout(k);
-      table[(size_t)k] = FieldMember{(unsigned long long)mem.pos_off, mem.n, 0};
-    }
-    FieldMember* dev = nullptr;
-    const int rc = device_table(r, &dev, table, where, "the member table");
-    if (rc) return rc;
-    r->field_tab = dev;
-  }
-  int columns = 1, row_splits = 1;
-  for (int k = first; k < first + count; ++k) {
-    const FieldShape s = field_shape(m, r->layout(k).n);
-    columns = s.columns;
-    row_splits = std::max(row_splits, s.splits);
-  }
+  const int rc = ragged_member_table<FieldMember>(r, &r->field_tab, &table, where, [](const MemberSpan& mem, unsigned long long) {
+    return FieldMember{(unsigned long long)mem.pos_off, mem.n, 0};
+  });
+  if (rc) return rc;
+  const GridExtents g = ragged_extents(r, first, count, m);  // m > 0: every member has the same columns
   const FieldMember* dev = (const FieldMember*)r->field_tab;
-  return run_field<T>(r, where, count, m, row_splits, dev, (unsigned)first, 0, a, [&](const T4* pts, T4* parts) {
+  return run_field<T>(r, where, count, m, g.splits, dev, (unsigned)first, 0, a, [&](const T4* pts, T4* parts) {
     RaggedFieldArgs<T> k{};
     k.posm = (const T4*)r->posm[r->cur];
     k.table = dev;
@@ -150,7 +120,7 @@ int field_members_t(nbx_ragged* r, const char* where, int first, int count, int 
     k.parts = parts;
     k.first = (unsigned)first;
     k.m = m;
-    hipLaunchKernelGGL(ragged_field_kernel<T>, dim3(columns, row_splits, count), dim3(kBlock), 0, r->stream, k);
+    hipLaunchKernelGGL(ragged_field_kernel<T>, dim3(g.columns, g.splits, count), dim3(kBlock), 0, r->stream, k);
   });
 }
 

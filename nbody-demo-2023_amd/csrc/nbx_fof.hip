@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/nbx_fof.h"
+#include "nbx_analysis.hpp"           // ensure_bytes, range_bodies, ragged_member_table, ragged_extents
 #include "nbx_ensemble_internal.hpp"  // struct nbx_ensemble; nbx_batch.hpp: check_range, check_uploaded, device_table
 #include "nbx_fof_kernels.hpp"
 #include "nbx_internal.hpp"         // struct nbx_ctx
@@ -27,20 +28,6 @@ using namespace nbx_detail;
 static_assert(sizeof(nbx_fof_info_t) == 2 * sizeof(int32_t), "the gather kernel writes {groups, largest} as two int32");
 
 namespace {
-
-// *p holds at least `bytes`: allocated on first use, replaced by a larger buffer -- never a smaller one -- when a call needs more
-int ensure_bytes(void** p, size_t* cap, size_t bytes, const char* where, const char* what) {
-  if (*p && *cap >= bytes) return NBX_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  char* dev = nullptr;
-  const int rc = device_alloc(&dev, bytes, where, what);
-  if (rc) return rc;
-  *p = dev;
-  *cap = bytes;
-  return NBX_OK;
-}
 
 struct Outputs {
   int32_t* label;
@@ -143,15 +130,6 @@ int fof_ctx_t(nbx_ctx* c, const char* where, double radius, const Outputs& a) {
   });
 }
 
-long long range_bodies(const nbx_ensemble* e, int, int count) { return (long long)count * e->n; }
-long long range_bodies(const nbx_ragged* r, int first, int count) {
-  long long total = 0;
-  for (int k = first; k < first + count; ++k) total += r->layout(k).n;
-  return total;
-}
-const char* range_noun(const nbx_ensemble*) { return "count * n exceeds"; }
-const char* range_noun(const nbx_ragged*) { return "the bodies of the range exceed"; }
-
 template <typename T>
 int fof_members_t(nbx_ensemble* e, const char* where, int first, int count, double radius, const Outputs& a) {
   using T4 = typename V4<T>::type;
@@ -176,34 +154,25 @@ template <typename T>
 int fof_members_t(nbx_ragged* r, const char* where, int first, int count, double radius, const Outputs& a) {
   using T4 = typename V4<T>::type;
   std::vector<FofMember> table;  // lives until run_fof has synchronised
-  if (!r->fof_tab) {
-    table.resize((size_t)r->members);
-    unsigned long long off = 0, rec_off = 0;
-    for (int k = 0; k < r->members; ++k) {
-      const MemberSpan mem = r->layout(k);
-      table[(size_t)k] = FofMember{(unsigned long long)mem.pos_off, off, rec_off, mem.n, 0};
-      off += (unsigned long long)mem.n;
-      rec_off += (unsigned long long)padded(mem.n);
-    }
-    FofMember* dev = nullptr;
-    const int rc = device_table(r, &dev, table, where, "the member table");
-    if (rc) return rc;
-    r->fof_tab = dev;
-  }
-  int columns = 1, row_splits = 1, n_max = 1;
-  size_t total = 0, rec_total = 0;
+  unsigned long long rec_off = 0;  // the staged records of the members before the one being made
+  const int rc = ragged_member_table<FofMember>(r, &r->fof_tab, &table, where, [&](const MemberSpan& mem, unsigned long long out_off) {
+    const FofMember entry{(unsigned long long)mem.pos_off, out_off, rec_off, mem.n, 0};
+    rec_off += (unsigned long long)padded(mem.n);
+    return entry;
+  });
+  if (rc) return rc;
+  const GridExtents ext = ragged_extents(r, first, count);
+  int n_max = 1;
+  size_t rec_total = 0;
   for (int k = first; k < first + count; ++k) {
     const int n = r->layout(k).n;
-    const FieldShape s = field_shape(n, n);
-    columns = std::max(columns, s.columns);
-    row_splits = std::max(row_splits, s.splits);
     n_max = std::max(n_max, n);
-    total += (size_t)n;
     rec_total += (size_t)padded(n);
   }
+  const size_t total = (size_t)range_bodies(r, first, count);
   const FofMember* dev = (const FofMember*)r->fof_tab;
   const FofRange g{dev, (unsigned)first, count, 0, 0u, 0u};
-  return run_fof<T>(r, where, g, total, rec_total, row_splits, n_max, a, [&](const T4* rec, int* parts) {
+  return run_fof<T>(r, where, g, total, rec_total, ext.splits, n_max, a, [&](const T4* rec, int* parts) {
     RaggedFofArgs<T> k{};
     k.rec = rec;
     k.table = dev;
@@ -211,7 +180,7 @@ int fof_members_t(nbx_ragged* r, const char* where, int first, int count, double
     k.h2 = radius2<T>(radius);
     k.first = (unsigned)first;
     k.total = (unsigned)total;
-    hipLaunchKernelGGL(ragged_fof_pass_kernel<T>, dim3(columns, row_splits, count), dim3(kBlock), 0, r->stream, k);
+    hipLaunchKernelGGL(ragged_fof_pass_kernel<T>, dim3(ext.columns, ext.splits, count), dim3(kBlock), 0, r->stream, k);
   });
 }
 

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/nbx_hermite.h"
+#include "nbx_analysis.hpp"           // object_bodies, bodies_noun, ragged_member_table, ragged_extents
 #include "nbx_ensemble_internal.hpp"  // struct nbx_ensemble; nbx_batch.hpp: check_uploaded
 #include "nbx_hermite_kernels.hpp"
 #include "nbx_internal.hpp"           // struct nbx_ctx
@@ -154,35 +155,17 @@ int hermite_t(nbx_ensemble* e, const char* where, double dt, int nsteps, int res
 template <typename T>
 int hermite_t(nbx_ragged* r, const char* where, double dt, int nsteps, int resume) {
   using T4 = typename V4<T>::type;
-  if (!r->herm_tab) {
-    std::vector<HermiteMember> table((size_t)r->members);
-    unsigned long long off = 0;
-    for (int k = 0; k < r->members; ++k) {
-      const MemberSpan mem = r->layout(k);
-      table[(size_t)k] = HermiteMember{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, off, mem.n, 0};
-      off += (unsigned long long)mem.n;
-    }
-    r->herm_tab_src.resize(sizeof(HermiteMember) * table.size());  // the copy's source lives with the object: nothing here waits for it
-    std::memcpy(r->herm_tab_src.data(), table.data(), r->herm_tab_src.size());
-    char* dev = nullptr;
-    const int rc = device_table(r, &dev, r->herm_tab_src, where, "the member table");
-    if (rc) return rc;
-    r->herm_tab = dev;
-  }
-  int columns = 1, row_splits = 1;
-  size_t total = 0;
-  for (int k = 0; k < r->members; ++k) {
-    const int n = r->layout(k).n;
-    const FieldShape s = field_shape(n, n);
-    columns = std::max(columns, s.columns);
-    row_splits = std::max(row_splits, s.splits);
-    total += (size_t)n;
-  }
+  // the copy's source, herm_tab_src, lives with the object: nothing here waits for it
+  const int rc = ragged_member_table<HermiteMember>(r, &r->herm_tab, &r->herm_tab_src, where, [](const MemberSpan& mem, unsigned long long out_off) {
+    return HermiteMember{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, out_off, mem.n, 0};
+  });
+  if (rc) return rc;
+  const GridExtents g = ragged_extents(r, 0, r->members);
   const HermiteMember* dev = (const HermiteMember*)r->herm_tab;
   HermiteFinishArgs<T> fin{};
   fin.table = dev;
   fin.members = r->members;
-  return run_hermite<T>(r, where, total, row_splits, span_of(r, 0, r->members).vel_count, dt, nsteps, resume, fin, [&](const PairLaunch<T>& p) {
+  return run_hermite<T>(r, where, (size_t)object_bodies(r), g.splits, span_of(r, 0, r->members).vel_count, dt, nsteps, resume, fin, [&](const PairLaunch<T>& p) {
     RaggedHermiteArgs<T> k{};
     k.posm = (const T4*)r->posm[r->cur];
     k.velm = (const T4*)r->velm;
@@ -191,18 +174,9 @@ int hermite_t(nbx_ragged* r, const char* where, double dt, int nsteps, int resum
     k.parts = p.parts;
     k.predict = p.predict;
     k.hc = p.hc;
-    hipLaunchKernelGGL(ragged_hermite_kernel<T>, dim3(columns, row_splits, r->members), dim3(kBlock), 0, r->stream, k);
+    hipLaunchKernelGGL(ragged_hermite_kernel<T>, dim3(g.columns, g.splits, r->members), dim3(kBlock), 0, r->stream, k);
   });
 }
-
-long long object_bodies(const nbx_ensemble* e) { return (long long)e->members * e->n; }
-long long object_bodies(const nbx_ragged* r) {
-  long long total = 0;
-  for (int k = 0; k < r->members; ++k) total += r->layout(k).n;
-  return total;
-}
-const char* bodies_noun(const nbx_ensemble*) { return "members * n exceeds"; }
-const char* bodies_noun(const nbx_ragged*) { return "the bodies of the members exceed"; }
 
 // dt as the object's precision holds it: a double that rounds to an infinite float is not a time step either
 bool dt_finite(int precision, double dt) { return std::isfinite(dt) && (precision != 32 || std::isfinite((float)dt)); }

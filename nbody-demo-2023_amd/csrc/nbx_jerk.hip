@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/nbx_jerk.h"
+#include "nbx_analysis.hpp"           // ensure_bytes, range_bodies, ragged_member_table, ragged_extents, read_back
 #include "nbx_ensemble_internal.hpp"  // struct nbx_ensemble; nbx_batch.hpp: check_range, check_uploaded, device_table
 #include "nbx_internal.hpp"           // struct nbx_ctx
 #include "nbx_jerk_kernels.hpp"
@@ -23,20 +24,6 @@ using namespace nbx;
 using namespace nbx_detail;
 
 namespace {
-
-// *p holds at least `bytes`: allocated on first use, replaced by a larger buffer -- never a smaller one -- when a call needs more
-int ensure_bytes(void** p, size_t* cap, size_t bytes, const char* where, const char* what) {
-  if (*p && *cap >= bytes) return NBX_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  char* dev = nullptr;
-  const int rc = device_alloc(&dev, bytes, where, what);
-  if (rc) return rc;
-  *p = dev;
-  *cap = bytes;
-  return NBX_OK;
-}
 
 bool no_output(const nbx_jerk_out_t& a) {
   for (int k = 0; k < 3; ++k)
@@ -55,20 +42,15 @@ int run_jerk(Object* o, const char* where, size_t total, int row_splits, const J
   rc = ensure_bytes(&o->jerk_out, &o->jerk_out_cap, sizeof(T4) * 2 * total, where, "the results");
   if (rc) return rc;
   std::vector<T4> res(2 * total);
-  const int rc_run = [&]() -> int {
+  rc = read_back(o, res.data(), o->jerk_out, sizeof(T4) * 2 * total, [&]() -> int {
     launch((T4*)o->jerk_part);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(jerk_finish_kernel<T>, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, o->stream,
                        (const T4*)o->jerk_part, table, first, count, n_all, row_splits, (unsigned)total, (T4*)o->jerk_out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(res.data(), o->jerk_out, sizeof(T4) * 2 * total, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
     return NBX_OK;
-  }();
-  if (rc_run) {
-    (void)hipStreamSynchronize(o->stream);  // no copy may outlive `res`
-    return rc_run;
-  }
+  });
+  if (rc) return rc;
   T* const ax = (T*)a.acc[0]; T* const ay = (T*)a.acc[1]; T* const az = (T*)a.acc[2];
   T* const jx = (T*)a.jerk[0]; T* const jy = (T*)a.jerk[1]; T* const jz = (T*)a.jerk[2];
   for (size_t i = 0; i < total; ++i) {
@@ -92,15 +74,6 @@ int jerk_ctx_t(nbx_ctx* c, const char* where, const nbx_jerk_out_t& a) {
                        c->n, s.tiles_per_split, parts);
   });
 }
-
-long long range_bodies(const nbx_ensemble* e, int, int count) { return (long long)count * e->n; }
-long long range_bodies(const nbx_ragged* r, int first, int count) {
-  long long total = 0;
-  for (int k = first; k < first + count; ++k) total += r->layout(k).n;
-  return total;
-}
-const char* range_noun(const nbx_ensemble*) { return "count * n exceeds"; }
-const char* range_noun(const nbx_ragged*) { return "the bodies of the range exceed"; }
 
 template <typename T>
 int jerk_members_t(nbx_ensemble* e, const char* where, int first, int count, const nbx_jerk_out_t& a) {
@@ -126,35 +99,20 @@ template <typename T>
 int jerk_members_t(nbx_ragged* r, const char* where, int first, int count, const nbx_jerk_out_t& a) {
   using T4 = typename V4<T>::type;
   std::vector<JerkMember> table;  // lives until run_jerk has synchronised
-  if (!r->jerk_tab) {
-    table.resize((size_t)r->members);
-    unsigned long long off = 0;
-    for (int k = 0; k < r->members; ++k) {
-      const MemberSpan mem = r->layout(k);
-      table[(size_t)k] = JerkMember{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, off, mem.n, 0};
-      off += (unsigned long long)mem.n;
-    }
-    JerkMember* dev = nullptr;
-    const int rc = device_table(r, &dev, table, where, "the member table");
-    if (rc) return rc;
-    r->jerk_tab = dev;
-  }
-  int columns = 1, row_splits = 1;
-  for (int k = first; k < first + count; ++k) {
-    const int n = r->layout(k).n;
-    const FieldShape s = field_shape(n, n);
-    columns = std::max(columns, s.columns);
-    row_splits = std::max(row_splits, s.splits);
-  }
+  const int rc = ragged_member_table<JerkMember>(r, &r->jerk_tab, &table, where, [](const MemberSpan& mem, unsigned long long out_off) {
+    return JerkMember{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, out_off, mem.n, 0};
+  });
+  if (rc) return rc;
+  const GridExtents g = ragged_extents(r, first, count);
   const JerkMember* dev = (const JerkMember*)r->jerk_tab;
-  return run_jerk<T>(r, where, (size_t)range_bodies(r, first, count), row_splits, dev, (unsigned)first, count, 0, a, [&](T4* parts) {
+  return run_jerk<T>(r, where, (size_t)range_bodies(r, first, count), g.splits, dev, (unsigned)first, count, 0, a, [&](T4* parts) {
     RaggedJerkArgs<T> k{};
     k.posm = (const T4*)r->posm[r->cur];
     k.velm = (const T4*)r->velm;
     k.table = dev;
     k.parts = parts;
     k.first = (unsigned)first;
-    hipLaunchKernelGGL(ragged_jerk_kernel<T>, dim3(columns, row_splits, count), dim3(kBlock), 0, r->stream, k);
+    hipLaunchKernelGGL(ragged_jerk_kernel<T>, dim3(g.columns, g.splits, count), dim3(kBlock), 0, r->stream, k);
   });
 }
 

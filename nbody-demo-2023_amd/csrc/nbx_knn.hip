@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/nbx_knn.h"
+#include "nbx_analysis.hpp"           // ensure_bytes, range_bodies, ragged_member_table, ragged_extents, read_back
 #include "nbx_ensemble_internal.hpp"  // struct nbx_ensemble; nbx_batch.hpp: check_range, check_uploaded, device_table
 #include "nbx_internal.hpp"           // struct nbx_ctx
 #include "nbx_knn_kernels.hpp"
@@ -26,20 +27,6 @@ using namespace nbx_detail;
 static_assert(kKnnMax == NBX_KNN_MAX && knn_capacity(NBX_KNN_MAX) == NBX_KNN_MAX, "the largest capacity serves the largest k");
 
 namespace {
-
-// *p holds at least `bytes`: allocated on first use, replaced by a larger buffer -- never a smaller one -- when a call needs more
-int ensure_bytes(void** p, size_t* cap, size_t bytes, const char* where, const char* what) {
-  if (*p && *cap >= bytes) return NBX_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  char* dev = nullptr;
-  const int rc = device_alloc(&dev, bytes, where, what);
-  if (rc) return rc;
-  *p = dev;
-  *cap = bytes;
-  return NBX_OK;
-}
 
 struct Outputs {
   int32_t* index;
@@ -71,7 +58,7 @@ int run_knn(Object* o, const char* where, size_t total, int row_splits, const Kn
   rc = ensure_bytes(&o->knn_out, &o->knn_out_cap, sizeof(Rec) * entries, where, "the results");
   if (rc) return rc;
   std::vector<Rec> res(entries);
-  const int rc_run = [&]() -> int {
+  rc = read_back(o, res.data(), o->knn_out, sizeof(Rec) * entries, [&]() -> int {
     launch((Rec*)o->knn_part);
     HIP_TRY(hipGetLastError());
     with_capacity(k, [&](auto cap) {
@@ -79,14 +66,9 @@ int run_knn(Object* o, const char* where, size_t total, int row_splits, const Kn
                          (const Rec*)o->knn_part, table, first, count, n_all, row_splits, k, (unsigned)total, (Rec*)o->knn_out);
     });
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(res.data(), o->knn_out, sizeof(Rec) * entries, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
     return NBX_OK;
-  }();
-  if (rc_run) {
-    (void)hipStreamSynchronize(o->stream);  // no copy may outlive `res`
-    return rc_run;
-  }
+  });
+  if (rc) return rc;
   T* r2 = (T*)a.r2;
   for (size_t i = 0; i < entries; ++i) {
     if (a.index) a.index[i] = res[i].j;
@@ -108,14 +90,9 @@ int knn_ctx_t(nbx_ctx* c, const char* where, int k, const Outputs& a) {
   });
 }
 
-long long range_bodies(const nbx_ensemble* e, int, int count) { return (long long)count * e->n; }
-long long range_bodies(const nbx_ragged* r, int first, int count) {
-  long long total = 0;
-  for (int m = first; m < first + count; ++m) total += r->layout(m).n;
-  return total;
-}
-const char* range_noun(const nbx_ensemble*) { return "count * n * k exceeds"; }
-const char* range_noun(const nbx_ragged*) { return "the bodies of the range times k exceed"; }
+// the words of the size bound, which here is on the entries: the bodies of the range times k
+const char* entries_noun(const nbx_ensemble*) { return "count * n * k exceeds"; }
+const char* entries_noun(const nbx_ragged*) { return "the bodies of the range times k exceed"; }
 
 template <typename T>
 int knn_members_t(nbx_ensemble* e, const char* where, int first, int count, int k, const Outputs& a) {
@@ -141,35 +118,20 @@ template <typename T>
 int knn_members_t(nbx_ragged* r, const char* where, int first, int count, int k, const Outputs& a) {
   using T4 = typename V4<T>::type;
   std::vector<KnnMember> table;  // lives until run_knn has synchronised
-  if (!r->knn_tab) {
-    table.resize((size_t)r->members);
-    unsigned long long off = 0;
-    for (int m = 0; m < r->members; ++m) {
-      const MemberSpan mem = r->layout(m);
-      table[(size_t)m] = KnnMember{(unsigned long long)mem.pos_off, off, mem.n, 0};
-      off += (unsigned long long)mem.n;
-    }
-    KnnMember* dev = nullptr;
-    const int rc = device_table(r, &dev, table, where, "the member table");
-    if (rc) return rc;
-    r->knn_tab = dev;
-  }
-  int columns = 1, row_splits = 1;
-  for (int m = first; m < first + count; ++m) {
-    const int n = r->layout(m).n;
-    const FieldShape s = field_shape(n, n);
-    columns = std::max(columns, s.columns);
-    row_splits = std::max(row_splits, s.splits);
-  }
+  const int rc = ragged_member_table<KnnMember>(r, &r->knn_tab, &table, where, [](const MemberSpan& mem, unsigned long long out_off) {
+    return KnnMember{(unsigned long long)mem.pos_off, out_off, mem.n, 0};
+  });
+  if (rc) return rc;
+  const GridExtents g = ragged_extents(r, first, count);
   const KnnMember* dev = (const KnnMember*)r->knn_tab;
-  return run_knn<T>(r, where, (size_t)range_bodies(r, first, count), row_splits, dev, (unsigned)first, count, 0, k, a, [&](KnnRecord<T>* parts) {
+  return run_knn<T>(r, where, (size_t)range_bodies(r, first, count), g.splits, dev, (unsigned)first, count, 0, k, a, [&](KnnRecord<T>* parts) {
     RaggedKnnArgs<T> w{};
     w.posm = (const T4*)r->posm[r->cur];
     w.table = dev;
     w.parts = parts;
     w.first = (unsigned)first;
     w.k = k;
-    const dim3 grid(columns, row_splits, count);
+    const dim3 grid(g.columns, g.splits, count);
     with_capacity(k, [&](auto cap) { hipLaunchKernelGGL((ragged_knn_kernel<T, decltype(cap)::value>), grid, dim3(kBlock), 0, r->stream, w); });
   });
 }
@@ -182,7 +144,7 @@ int batch_knn(O* o, const char* where, int32_t first, int32_t count, int32_t k, 
   if (bad_k(k)) return fail(NBX_ERR_ARG, std::string(where) + ": k is outside [1, 16]");
   int rc = check_range(o, where, first, count);
   if (rc) return rc;
-  if (range_bodies(o, first, count) * (long long)k > kKnnMaxEntries) return fail(NBX_ERR_ARG, std::string(where) + ": " + range_noun(o) + " 4194304");
+  if (range_bodies(o, first, count) * (long long)k > kKnnMaxEntries) return fail(NBX_ERR_ARG, std::string(where) + ": " + entries_noun(o) + " 4194304");
   rc = check_uploaded(o, where, first, count);
   if (rc) return rc;
   if (count == 0 || no_output(a)) return NBX_OK;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/nbx_neighbours.h"
+#include "nbx_analysis.hpp"           // ensure_bytes, range_bodies, ragged_member_table, ragged_extents, read_back
 #include "nbx_ensemble_internal.hpp"  // struct nbx_ensemble; nbx_batch.hpp: check_range, check_uploaded, device_table
 #include "nbx_internal.hpp"           // struct nbx_ctx
 #include "nbx_neighbours_kernels.hpp"
@@ -25,20 +26,6 @@ using namespace nbx;
 using namespace nbx_detail;
 
 namespace {
-
-// *p holds at least `bytes`: allocated on first use, replaced by a larger buffer -- never a smaller one -- when a call needs more
-int ensure_bytes(void** p, size_t* cap, size_t bytes, const char* where, const char* what) {
-  if (*p && *cap >= bytes) return NBX_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  char* dev = nullptr;
-  const int rc = device_alloc(&dev, bytes, where, what);
-  if (rc) return rc;
-  *p = dev;
-  *cap = bytes;
-  return NBX_OK;
-}
 
 struct Outputs {
   int32_t* index;
@@ -67,20 +54,15 @@ int run_neighbours(Object* o, const char* where, size_t total, int row_splits, c
   rc = ensure_bytes(&o->nb_out, &o->nb_out_cap, sizeof(Rec) * total, where, "the results");
   if (rc) return rc;
   std::vector<Rec> res(total);
-  const int rc_run = [&]() -> int {
+  rc = read_back(o, res.data(), o->nb_out, sizeof(Rec) * total, [&]() -> int {
     launch((Rec*)o->nb_part);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(neighbour_finish_kernel<T>, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, o->stream,
                        (const Rec*)o->nb_part, table, first, count, n_all, row_splits, (unsigned)total, (Rec*)o->nb_out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(res.data(), o->nb_out, sizeof(Rec) * total, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
     return NBX_OK;
-  }();
-  if (rc_run) {
-    (void)hipStreamSynchronize(o->stream);  // no copy may outlive `res`
-    return rc_run;
-  }
+  });
+  if (rc) return rc;
   T* r2 = (T*)a.r2;
   for (size_t i = 0; i < total; ++i) {
     if (a.index) a.index[i] = res[i].j;
@@ -105,15 +87,6 @@ int neighbours_ctx_t(nbx_ctx* c, const char* where, double radius, const Outputs
                          parts);
   });
 }
-
-long long range_bodies(const nbx_ensemble* e, int, int count) { return (long long)count * e->n; }
-long long range_bodies(const nbx_ragged* r, int first, int count) {
-  long long total = 0;
-  for (int k = first; k < first + count; ++k) total += r->layout(k).n;
-  return total;
-}
-const char* range_noun(const nbx_ensemble*) { return "count * n exceeds"; }
-const char* range_noun(const nbx_ragged*) { return "the bodies of the range exceed"; }
 
 template <typename T>
 int neighbours_members_t(nbx_ensemble* e, const char* where, int first, int count, double radius, const Outputs& a) {
@@ -140,35 +113,20 @@ template <typename T>
 int neighbours_members_t(nbx_ragged* r, const char* where, int first, int count, double radius, const Outputs& a) {
   using T4 = typename V4<T>::type;
   std::vector<NbMember> table;  // lives until run_neighbours has synchronised
-  if (!r->nb_tab) {
-    table.resize((size_t)r->members);
-    unsigned long long off = 0;
-    for (int k = 0; k < r->members; ++k) {
-      const MemberSpan mem = r->layout(k);
-      table[(size_t)k] = NbMember{(unsigned long long)mem.pos_off, off, mem.n, 0};
-      off += (unsigned long long)mem.n;
-    }
-    NbMember* dev = nullptr;
-    const int rc = device_table(r, &dev, table, where, "the member table");
-    if (rc) return rc;
-    r->nb_tab = dev;
-  }
-  int columns = 1, row_splits = 1;
-  for (int k = first; k < first + count; ++k) {
-    const int n = r->layout(k).n;
-    const FieldShape s = field_shape(n, n);
-    columns = std::max(columns, s.columns);
-    row_splits = std::max(row_splits, s.splits);
-  }
+  const int rc = ragged_member_table<NbMember>(r, &r->nb_tab, &table, where, [](const MemberSpan& mem, unsigned long long out_off) {
+    return NbMember{(unsigned long long)mem.pos_off, out_off, mem.n, 0};
+  });
+  if (rc) return rc;
+  const GridExtents g = ragged_extents(r, first, count);
   const NbMember* dev = (const NbMember*)r->nb_tab;
-  return run_neighbours<T>(r, where, (size_t)range_bodies(r, first, count), row_splits, dev, (unsigned)first, count, 0, a, [&](NbRecord<T>* parts) {
+  return run_neighbours<T>(r, where, (size_t)range_bodies(r, first, count), g.splits, dev, (unsigned)first, count, 0, a, [&](NbRecord<T>* parts) {
     RaggedNbArgs<T> k{};
     k.posm = (const T4*)r->posm[r->cur];
     k.table = dev;
     k.parts = parts;
     k.h2 = radius2<T>(radius);
     k.first = (unsigned)first;
-    const dim3 grid(columns, row_splits, count);
+    const dim3 grid(g.columns, g.splits, count);
     if (a.within) hipLaunchKernelGGL((ragged_neighbour_kernel<T, true>), grid, dim3(kBlock), 0, r->stream, k);
     else hipLaunchKernelGGL((ragged_neighbour_kernel<T, false>), grid, dim3(kBlock), 0, r->stream, k);
   });

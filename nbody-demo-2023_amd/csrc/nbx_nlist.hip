@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/nbx_nlist.h"
+#include "nbx_analysis.hpp"           // ensure_bytes, range_bodies, ragged_member_table, ragged_extents
 #include "nbx_ensemble_internal.hpp"  // struct nbx_ensemble; nbx_batch.hpp: check_range, check_uploaded, device_table
 #include "nbx_internal.hpp"           // struct nbx_ctx
 #include "nbx_nlist_kernels.hpp"
@@ -28,20 +29,6 @@ using namespace nbx_detail;
 static_assert(sizeof(long long) == sizeof(int64_t), "offsets are scanned as long long and handed out as int64_t");
 
 namespace {
-
-// *p holds at least `bytes`: allocated on first use, replaced by a larger buffer -- never a smaller one -- when a call needs more
-int ensure_bytes(void** p, size_t* cap, size_t bytes, const char* where, const char* what) {
-  if (*p && *cap >= bytes) return NBX_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  char* dev = nullptr;
-  const int rc = device_alloc(&dev, bytes, where, what);
-  if (rc) return rc;
-  *p = dev;
-  *cap = bytes;
-  return NBX_OK;
-}
 
 struct Outputs {
   int64_t capacity;
@@ -141,15 +128,6 @@ int nlist_ctx_t(nbx_ctx* c, const char* where, double radius, const Outputs& a) 
       });
 }
 
-long long range_bodies(const nbx_ensemble* e, int, int count) { return (long long)count * e->n; }
-long long range_bodies(const nbx_ragged* r, int first, int count) {
-  long long total = 0;
-  for (int k = first; k < first + count; ++k) total += r->layout(k).n;
-  return total;
-}
-const char* range_noun(const nbx_ensemble*) { return "count * n exceeds"; }
-const char* range_noun(const nbx_ragged*) { return "the bodies of the range exceed"; }
-
 template <typename T>
 int nlist_members_t(nbx_ensemble* e, const char* where, int first, int count, double radius, const Outputs& a) {
   using T4 = typename V4<T>::type;
@@ -180,35 +158,20 @@ template <typename T>
 int nlist_members_t(nbx_ragged* r, const char* where, int first, int count, double radius, const Outputs& a) {
   using T4 = typename V4<T>::type;
   std::vector<NlMember> table;  // lives until run_nlist has synchronised
-  if (!r->nl_tab) {
-    table.resize((size_t)r->members);
-    unsigned long long off = 0;
-    for (int k = 0; k < r->members; ++k) {
-      const MemberSpan mem = r->layout(k);
-      table[(size_t)k] = NlMember{(unsigned long long)mem.pos_off, off, mem.n, 0};
-      off += (unsigned long long)mem.n;
-    }
-    NlMember* dev = nullptr;
-    const int rc = device_table(r, &dev, table, where, "the member table");
-    if (rc) return rc;
-    r->nl_tab = dev;
-  }
-  int columns = 1, row_splits = 1;
-  for (int k = first; k < first + count; ++k) {
-    const int n = r->layout(k).n;
-    const FieldShape s = field_shape(n, n);
-    columns = std::max(columns, s.columns);
-    row_splits = std::max(row_splits, s.splits);
-  }
+  const int rc = ragged_member_table<NlMember>(r, &r->nl_tab, &table, where, [](const MemberSpan& mem, unsigned long long out_off) {
+    return NlMember{(unsigned long long)mem.pos_off, out_off, mem.n, 0};
+  });
+  if (rc) return rc;
+  const GridExtents g = ragged_extents(r, first, count);
   const NlMember* dev = (const NlMember*)r->nl_tab;
   RaggedNlArgs<T> k{};
   k.posm = (const T4*)r->posm[r->cur];
   k.table = dev;
   k.h2 = radius2<T>(radius);
   k.first = (unsigned)first;
-  const dim3 grid(columns, row_splits, count);
+  const dim3 grid(g.columns, g.splits, count);
   return run_nlist<T>(
-      r, where, (size_t)range_bodies(r, first, count), row_splits, dev, (unsigned)first, count, 0, a,
+      r, where, (size_t)range_bodies(r, first, count), g.splits, dev, (unsigned)first, count, 0, a,
       [&](NlSegment* seg) {
         k.seg = seg;
         hipLaunchKernelGGL((ragged_nlist_kernel<T, false>), grid, dim3(kBlock), 0, r->stream, k, NlLists<T>{});

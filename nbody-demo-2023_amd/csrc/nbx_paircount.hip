@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/nbx_paircount.h"
+#include "nbx_analysis.hpp"           // ensure_bytes, range_bodies, ragged_member_table, ragged_extents, read_back
 #include "nbx_ensemble_internal.hpp"  // struct nbx_ensemble; nbx_batch.hpp: check_range, check_uploaded, device_table
 #include "nbx_internal.hpp"           // struct nbx_ctx
 #include "nbx_paircount_kernels.hpp"
@@ -42,20 +43,6 @@ bool wave_scheme() {
     if (!strcmp(e, "lane")) return false;
   }
   return kPcDefaultWave;
-}
-
-// *p holds at least `bytes`: allocated on first use, replaced by a larger buffer -- never a smaller one -- when a call needs more
-int ensure_bytes(void** p, size_t* cap, size_t bytes, const char* where, const char* what) {
-  if (*p && *cap >= bytes) return NBX_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  char* dev = nullptr;
-  const int rc = device_alloc(&dev, bytes, where, what);
-  if (rc) return rc;
-  *p = dev;
-  *cap = bytes;
-  return NBX_OK;
 }
 
 // statuses 2 and 3 of the header
@@ -111,7 +98,7 @@ int run_paircount(Object* o, const char* where, int count, int nradii, int row_c
   if (rc) return rc;
   static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the device's counts are the caller's");
   const bool wave = wave_scheme();
-  const int rc_run = [&]() -> int {
+  return read_back(o, counts, o->pc_out, sizeof(uint64_t) * total, [&]() -> int {
     for (int pass = 0; pass < passes; ++pass) {
       with_instance(nradii - pass * kPcSlots, wave,
                     [&](auto e, auto w) { launch(e, w, pass, (unsigned*)o->pc_part + (size_t)pass * pass_stride, member_stride); });
@@ -121,12 +108,8 @@ int run_paircount(Object* o, const char* where, int count, int nradii, int row_c
                        (const unsigned*)o->pc_part, table, first, nradii, n_all, passes, row_splits, row_columns, (unsigned)total,
                        (unsigned long long*)o->pc_out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(counts, o->pc_out, sizeof(uint64_t) * total, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
     return NBX_OK;
-  }();
-  if (rc_run) (void)hipStreamSynchronize(o->stream);  // no copy may outlive the call
-  return rc_run;
+  });
 }
 
 template <typename T>
@@ -141,15 +124,6 @@ int paircount_ctx_t(nbx_ctx* c, const char* where, int nradii, const double* rad
                                             (const T4*)c->posm[c->cur], c->n, s.tiles_per_split, pass_radii<T, E>(radii, nradii, pass), parts);
                        });
 }
-
-long long range_bodies(const nbx_ensemble* e, int, int count) { return (long long)count * e->n; }
-long long range_bodies(const nbx_ragged* r, int first, int count) {
-  long long total = 0;
-  for (int k = first; k < first + count; ++k) total += r->layout(k).n;
-  return total;
-}
-const char* range_noun(const nbx_ensemble*) { return "count * n exceeds"; }
-const char* range_noun(const nbx_ragged*) { return "the bodies of the range exceed"; }
 
 template <typename T>
 int paircount_members_t(nbx_ensemble* en, const char* where, int first, int count, int nradii, const double* radii, uint64_t* counts) {
@@ -178,26 +152,13 @@ template <typename T>
 int paircount_members_t(nbx_ragged* r, const char* where, int first, int count, int nradii, const double* radii, uint64_t* counts) {
   using T4 = typename V4<T>::type;
   std::vector<PcMember> table;  // lives until run_paircount has synchronised
-  if (!r->pc_tab) {
-    table.resize((size_t)r->members);
-    for (int k = 0; k < r->members; ++k) {
-      const MemberSpan mem = r->layout(k);
-      table[(size_t)k] = PcMember{(unsigned long long)mem.pos_off, mem.n, 0};
-    }
-    PcMember* dev = nullptr;
-    const int rc = device_table(r, &dev, table, where, "the member table");
-    if (rc) return rc;
-    r->pc_tab = dev;
-  }
-  int columns = 1, row_splits = 1;
-  for (int k = first; k < first + count; ++k) {
-    const int n = r->layout(k).n;
-    const FieldShape s = field_shape(n, n);
-    columns = std::max(columns, s.columns);
-    row_splits = std::max(row_splits, s.splits);
-  }
+  int rc = ragged_member_table<PcMember>(r, &r->pc_tab, &table, where, [](const MemberSpan& mem, unsigned long long) {
+    return PcMember{(unsigned long long)mem.pos_off, mem.n, 0};
+  });
+  if (rc) return rc;
+  const GridExtents g = ragged_extents(r, first, count);
   const PcMember* dev = (const PcMember*)r->pc_tab;
-  const int rc = run_paircount(r, where, count, nradii, columns, row_splits, dev, (unsigned)first, 0, counts,
+  rc = run_paircount(r, where, count, nradii, g.columns, g.splits, dev, (unsigned)first, 0, counts,
                                [&](auto e, auto w, int pass, unsigned* parts, size_t member_stride) {
                                  constexpr int E = decltype(e)::value;
                                  constexpr bool W = decltype(w)::value;
@@ -208,7 +169,7 @@ int paircount_members_t(nbx_ragged* r, const char* where, int first, int count, 
                                  k.member_stride = member_stride;
                                  k.h = pass_radii<T, E>(radii, nradii, pass);
                                  k.first = (unsigned)first;
-                                 hipLaunchKernelGGL((ragged_paircount_kernel<T, E, W>), dim3(columns, row_splits, count), dim3(kBlock), 0, r->stream, k);
+                                 hipLaunchKernelGGL((ragged_paircount_kernel<T, E, W>), dim3(g.columns, g.splits, count), dim3(kBlock), 0, r->stream, k);
                                });
   if (rc && !table.empty()) (void)hipStreamSynchronize(r->stream);  // the table's copy may not outlive `table`
   return rc;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/nbx_tidal.h"
+#include "nbx_analysis.hpp"           // ensure_bytes, range_bodies, ragged_member_table, ragged_extents, read_back
 #include "nbx_ensemble_internal.hpp"  // struct nbx_ensemble; nbx_batch.hpp: check_range, check_uploaded, device_table
 #include "nbx_internal.hpp"           // struct nbx_ctx
 #include "nbx_ragged_internal.hpp"    // struct nbx_ragged
@@ -25,20 +26,6 @@ using namespace nbx;
 using namespace nbx_detail;
 
 namespace {
-
-// *p holds at least `bytes`: allocated on first use, replaced by a larger buffer -- never a smaller one -- when a call needs more
-int ensure_bytes(void** p, size_t* cap, size_t bytes, const char* where, const char* what) {
-  if (*p && *cap >= bytes) return NBX_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  char* dev = nullptr;
-  const int rc = device_alloc(&dev, bytes, where, what);
-  if (rc) return rc;
-  *p = dev;
-  *cap = bytes;
-  return NBX_OK;
-}
 
 // points == nullptr: bodies mode
 struct Points {
@@ -78,21 +65,16 @@ int run_tidal(Object* o, const char* where, size_t total, int count, int m, int 
     }
   }
   std::vector<T4> res(2 * total);  // not `host`: the points may still be leaving it
-  const int rc_run = [&]() -> int {
+  rc = read_back(o, res.data(), o->tidal_out, 2 * sizeof(T4) * total, [&]() -> int {
     if (p) HIP_TRY(hipMemcpyAsync(o->tidal_pts, host.data(), sizeof(T4) * total, hipMemcpyHostToDevice, o->stream));
     launch((const T4*)o->tidal_pts, (T4*)o->tidal_part);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(tidal_finish_kernel<T>, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, o->stream,
                        (const T4*)o->tidal_part, table, first, count, n_all, m, row_splits, (unsigned)total, (T4*)o->tidal_out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(res.data(), o->tidal_out, 2 * sizeof(T4) * total, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
     return NBX_OK;
-  }();
-  if (rc_run) {
-    (void)hipStreamSynchronize(o->stream);  // no copy may outlive `host` and `res`
-    return rc_run;
-  }
+  });
+  if (rc) return rc;  // read_back has synchronised: no copy outlives `host` and `res`
   T* out[6];
   for (int c = 0; c < 6; ++c) out[c] = (T*)t[c];
   for (size_t i = 0; i < total; ++i) {
@@ -143,44 +125,20 @@ int tidal_members_t(nbx_ensemble* e, const char* where, int first, int count, in
   });
 }
 
-long long range_bodies(const nbx_ensemble* e, int, int count) { return (long long)count * e->n; }
-long long range_bodies(const nbx_ragged* r, int first, int count) {
-  long long total = 0;
-  for (int k = first; k < first + count; ++k) total += r->layout(k).n;
-  return total;
-}
-const char* range_noun(const nbx_ensemble*) { return "count * n exceeds"; }
-const char* range_noun(const nbx_ragged*) { return "the bodies of the range exceed"; }
-
 // The member table is built and put on the device by the first call of either mode; the grid's x and y extents are the largest
 // number of columns and of splits any member of the range has, a member's workgroups beyond its own return at once.
 template <typename T>
 int tidal_members_t(nbx_ragged* r, const char* where, int first, int count, int m, const Points* p, void* const* t) {
   using T4 = typename V4<T>::type;
   std::vector<TidalMember> table;  // lives until run_tidal has synchronised
-  if (!r->tidal_tab) {
-    table.resize((size_t)r->members);
-    unsigned long long off = 0;
-    for (int k = 0; k < r->members; ++k) {
-      const MemberSpan mem = r->layout(k);
-      table[(size_t)k] = TidalMember{(unsigned long long)mem.pos_off, off, mem.n, 0};
-      off += (unsigned long long)mem.n;
-    }
-    TidalMember* dev = nullptr;
-    const int rc = device_table(r, &dev, table, where, "the member table");
-    if (rc) return rc;
-    r->tidal_tab = dev;
-  }
-  int columns = 1, row_splits = 1;
-  for (int k = first; k < first + count; ++k) {
-    const int n = r->layout(k).n;
-    const FieldShape s = field_shape(p ? m : n, n);
-    columns = std::max(columns, s.columns);
-    row_splits = std::max(row_splits, s.splits);
-  }
+  const int rc = ragged_member_table<TidalMember>(r, &r->tidal_tab, &table, where, [](const MemberSpan& mem, unsigned long long out_off) {
+    return TidalMember{(unsigned long long)mem.pos_off, out_off, mem.n, 0};
+  });
+  if (rc) return rc;
+  const GridExtents g = ragged_extents(r, first, count, p ? m : 0);
   const size_t total = p ? (size_t)count * (size_t)m : (size_t)range_bodies(r, first, count);
   const TidalMember* dev = (const TidalMember*)r->tidal_tab;
-  return run_tidal<T>(r, where, total, count, p ? m : 0, row_splits, dev, (unsigned)first, 0, p, t, [&](const T4* dpts, T4* parts) {
+  return run_tidal<T>(r, where, total, count, p ? m : 0, g.splits, dev, (unsigned)first, 0, p, t, [&](const T4* dpts, T4* parts) {
     RaggedTidalArgs<T> k{};
     k.posm = (const T4*)r->posm[r->cur];
     k.table = dev;
@@ -188,7 +146,7 @@ int tidal_members_t(nbx_ragged* r, const char* where, int first, int count, int 
     k.parts = parts;
     k.first = (unsigned)first;
     k.m = m;
-    const dim3 grid(columns, row_splits, count);
+    const dim3 grid(g.columns, g.splits, count);
     if (p) hipLaunchKernelGGL((ragged_tidal_kernel<T, false>), grid, dim3(kBlock), 0, r->stream, k);
     else hipLaunchKernelGGL((ragged_tidal_kernel<T, true>), grid, dim3(kBlock), 0, r->stream, k);
   });

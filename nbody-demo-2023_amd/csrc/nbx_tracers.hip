@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/nbx_tracers.h"
+#include "nbx_analysis.hpp"           // ensure_bytes, ragged_member_table
 #include "nbx_ensemble_internal.hpp"  // struct nbx_ensemble; nbx_batch.hpp: check_range, check_uploaded, enqueue_step
 #include "nbx_internal.hpp"           // struct nbx_ctx; enqueue_one_step, enqueue_ke_reduce
 #include "nbx_ragged_internal.hpp"    // struct nbx_ragged
@@ -143,35 +144,13 @@ int enqueue_tracers_any(O* o, double h) {
 // ---------------------------------------------------------------------------------------------------------------------------
 // buffers
 // ---------------------------------------------------------------------------------------------------------------------------
-// *p holds at least `bytes`: allocated on first use, replaced by a larger buffer -- never a smaller one -- when a set needs more
-int ensure_bytes(void** p, size_t* cap, size_t bytes, const char* where, const char* what) {
-  if (*p && *cap >= bytes) return NBX_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  char* dev = nullptr;
-  const int rc = device_alloc(&dev, bytes, where, what);
-  if (rc) return rc;
-  *p = dev;
-  *cap = bytes;
-  return NBX_OK;
-}
-
 int ensure_table(nbx_ctx*, const char*, std::vector<TracerMember>*) { return NBX_OK; }
 int ensure_table(nbx_ensemble*, const char*, std::vector<TracerMember>*) { return NBX_OK; }
 // `table` lives until the caller has synchronised
 int ensure_table(nbx_ragged* r, const char* where, std::vector<TracerMember>* table) {
-  if (r->tr_tab) return NBX_OK;
-  table->resize((size_t)r->members);
-  for (int k = 0; k < r->members; ++k) {
-    const MemberSpan mem = r->layout(k);
-    (*table)[(size_t)k] = TracerMember{(unsigned long long)mem.pos_off, mem.n, 0};
-  }
-  TracerMember* dev = nullptr;
-  const int rc = device_table(r, &dev, *table, where, "the member table");
-  if (rc) return rc;
-  r->tr_tab = dev;
-  return NBX_OK;
+  return ragged_member_table<TracerMember>(r, &r->tr_tab, table, where, [](const MemberSpan& mem, unsigned long long) {
+    return TracerMember{(unsigned long long)mem.pos_off, mem.n, 0};
+  });
 }
 
 void forget(Object* o) {

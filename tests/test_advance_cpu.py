@@ -21,6 +21,7 @@ from energy_ref import G32
 
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "nbx_advance.hip")
+ANALYSIS = os.path.join(CSRC, "nbx_analysis.hpp")  # the host layer the analysis calls share
 KERNELS = "nbx_advance_kernels.hpp"
 ADVANCE = ("nbx_advance", "nbx_ensemble_advance", "nbx_ragged_advance")
 CLOCK = ("nbx_clock", "nbx_ensemble_clock", "nbx_ragged_clock")
@@ -227,6 +228,10 @@ def test_the_checks_are_in_the_source_in_the_headers_order_and_only_the_clock_ca
     advance = src[:src.index("bool size_ok(")] + ctx
     assert "hipStreamSynchronize" not in advance and "hipDeviceSynchronize" not in advance and "DeviceToHost" not in advance
     assert "hipMemcpy" not in advance  # the one copy, of the ragged member table, is device_table's, from bytes that live with the object
+    shared = re.sub(r"//.*", "", open(ANALYSIS).read())  # which ragged_member_table reaches; the batch kinds' size-bound words are shared too
+    assert "&r->herm_tab, &r->herm_tab_src" in advance and "device_table(" in shared and "device_table(" not in src
+    assert '"members * n exceeds"' in shared and '"the bodies of the members exceed"' in shared
+    assert "object_bodies(o) > kAdvanceMaxBodies" in args and "bodies_noun(o)" in args and '"n exceeds"' in src
     assert "timed_launch" not in src and "steps_done +=" not in src and "cur ^=" not in src
     assert "o->herm_have = false;" in advance
     # the clock path: one read-back and one synchronisation, in one helper every kind goes through

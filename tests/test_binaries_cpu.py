@@ -31,6 +31,7 @@ from field_ref import field_shape
 
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "nbx_binaries.hip")
+ANALYSIS = os.path.join(CSRC, "nbx_analysis.hpp")  # the host layer the analysis calls share
 KERNELS = "nbx_binaries_kernels.hpp"
 OTHER_HEADERS = ("nbx.h", "nbx_diag.h", "nbx_ensemble.h", "nbx_ensemble_diag.h", "nbx_ragged.h", "nbx_ragged_diag.h", "nbx_batch_accel.h",
                  "nbx_kick.h", "nbx_timescale.h", "nbx_field.h", "nbx_neighbours.h", "nbx_paircount.h", "nbx_tracers.h", "nbx_knn.h",
@@ -156,8 +157,9 @@ def test_the_size_bound_and_the_refusal_of_a_sliced_context_are_in_the_source_in
     src = re.sub(r"//.*", "", open(SRC).read())
     hdr = re.sub(r"//.*", "", open(os.path.join(CSRC, KERNELS)).read())
     assert "constexpr long long kBoundMaxBodies = kFieldMaxPoints;" in hdr
-    assert '"nbx_binaries: n exceeds 4194304"' in src and '"count * n exceeds"' in src and '"the bodies of the range exceed"' in src
-    assert "(long long)c->n > kBoundMaxBodies" in src and "range_bodies(o, first, count) > kBoundMaxBodies" in src
+    shared = re.sub(r"//.*", "", open(ANALYSIS).read())  # range_bodies and range_noun: one definition for every call
+    assert '"nbx_binaries: n exceeds 4194304"' in src and '"count * n exceeds"' in shared and '"the bodies of the range exceed"' in shared
+    assert "(long long)c->n > kBoundMaxBodies" in src and "range_bodies(o, first, count) > kBoundMaxBodies" in src and "range_noun(o)" in src
     batch = src[src.index("int batch_binaries("):]
     order = [batch.index(w) for w in ("is NULL", "check_range(", "kBoundMaxBodies", "check_uploaded(", "no_output(a)", "use_device(")]
     assert order == sorted(order)
@@ -170,7 +172,12 @@ def test_the_size_bound_and_the_refusal_of_a_sliced_context_are_in_the_source_in
     assert 'fail(NBX_ERR_STATE, "nbx_binaries: %s")' % text in ctx
     assert '"nbx_timescale: %s"' % text in open(os.path.join(CSRC, "nbx_timescale.hip")).read()
     assert '"nbx_binaries: a local step awaits nbx_commit"' in ctx
-    assert len(re.findall(r"hipStreamSynchronize\(o->stream\)", src)) == 2  # one synchronisation, and the one of the failure path
+    # the read-back is the shared skeleton's: no synchronisation of the call's own, one use of the helper, and in the helper's body
+    # one synchronisation and the one of the failure path
+    assert "hipStreamSynchronize" not in src and len(re.findall(r"\bread_back\(", src)) == 1
+    helper = shared[shared.index("int read_back("):]
+    helper = helper[:helper.index("\n}\n")]
+    assert len(re.findall(r"hipStreamSynchronize\(o->stream\)", helper)) == 2 and len(re.findall(r"hipStreamSynchronize\(", helper)) == 2
 
 
 def test_python_methods_keys_and_the_helper_are_as_specified(nbx):
@@ -195,7 +202,7 @@ def test_the_build_files_compile_and_link_the_translation_unit():
     rule = re.search(r"^\$\(PKG\)/nbx_binaries\.o: \$\(CSRC\)/nbx_binaries\.hip(.*)\n\t\$\(HIPCC\) \$\(HIPFLAGS\) -c \$< -o \$@$", mk, re.M)
     knn = re.search(r"^\$\(PKG\)/nbx_knn\.o: \$\(CSRC\)/nbx_knn\.hip(.*)\n", mk, re.M)
     assert rule and rule.group(1) == knn.group(1).replace("knn", "binaries")  # the same dependency list
-    for dep in (KERNELS, "nbx_field_shape.hpp", "nbx_ensemble_internal.hpp", "nbx_ragged_internal.hpp", "nbx_internal.hpp",
+    for dep in (KERNELS, "nbx_analysis.hpp", "nbx_field_shape.hpp", "nbx_ensemble_internal.hpp", "nbx_ragged_internal.hpp", "nbx_internal.hpp",
                 "nbx_batch.hpp", "nbx_object.hpp", "nbx_plan.hpp", "nbx_diag_shape.hpp", "nbx_pair.hpp", "include/nbx_binaries.h",
                 "include/nbx_ensemble.h", "include/nbx_ragged.h", "include/nbx.h", "include/nbx_diag.h"):
         assert dep in rule.group(1), dep
@@ -224,8 +231,11 @@ def test_the_kernels_live_in_their_own_translation_unit_reuse_the_shape_rule_and
     assert "atomic" not in both
     assert "__shared__ T4 ptile[kTile];" in kern and "__shared__ T4 vtile[kTile];" in kern  # two arrays per tile
     assert "if (j < n) next_v = velm[j];" in kern and re.sub(r"//.*", "", kern).count("velm[") == 3  # a velocity is loaded only below n
-    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "device_alloc(", "device_table("):
+    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "ensure_bytes(", "ragged_member_table<", "ragged_extents(", "read_back("):
         assert fn in src, fn
+    shared = open(ANALYSIS).read()  # device_alloc and device_table are reached through ensure_bytes and ragged_member_table
+    for fn in ("device_alloc(", "device_table("):
+        assert fn in shared and fn not in re.sub(r"//.*", "", src), fn
     obj = open(os.path.join(CSRC, "nbx_object.hpp")).read()
     for field in ("bin_part", "bin_out", "bin_tab"):
         assert re.search(r"void\* %s = nullptr;" % field, obj) and "o->%s" % field in obj[obj.index("inline void batch_release"):], field

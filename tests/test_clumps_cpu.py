@@ -29,6 +29,7 @@ from energy_ref import EPS2
 
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "nbx_clumps.hip")
+ANALYSIS = os.path.join(CSRC, "nbx_analysis.hpp")  # the host layer the analysis calls share
 KERNELS = "nbx_clumps_kernels.hpp"
 ENTRY_POINTS = ("nbx_clumps", "nbx_ensemble_clumps", "nbx_ragged_clumps")
 NOUN = {"nbx_clumps": "ctx", "nbx_ensemble_clumps": "ensemble", "nbx_ragged_clumps": "ragged ensemble"}
@@ -159,7 +160,9 @@ def test_the_size_bound_and_the_refusal_of_a_sliced_context_are_in_the_source_in
     src = re.sub(r"//.*", "", open(SRC).read())
     hdr = re.sub(r"//.*", "", open(os.path.join(CSRC, KERNELS)).read())
     assert "constexpr long long kClumpMaxBodies = kFieldMaxPoints;" in hdr
-    assert '"nbx_clumps: n exceeds 4194304"' in src and '"count * n exceeds"' in src and '"the bodies of the range exceed"' in src
+    shared = re.sub(r"//.*", "", open(ANALYSIS).read())  # range_bodies and range_noun: one definition for every call
+    assert '"nbx_clumps: n exceeds 4194304"' in src and '"count * n exceeds"' in shared and '"the bodies of the range exceed"' in shared
+    assert "(long long)c->n > kClumpMaxBodies" in src and "range_bodies(o, first, count) > kClumpMaxBodies" in src and "range_noun(o)" in src
     batch = src[src.index("int batch_clumps("):]
     order = [batch.index(w) for w in ("is NULL", "label or out is NULL", "check_range(", "kClumpMaxBodies", "check_uploaded(", "no_output(*out)",
                                       "use_device(")]
@@ -170,9 +173,17 @@ def test_the_size_bound_and_the_refusal_of_a_sliced_context_are_in_the_source_in
     assert order == sorted(order)
     text = "the context owns a slice of the bodies (the velocities of the others are not resident)"
     assert 'fail(NBX_ERR_STATE, "nbx_clumps: %s")' % text in ctx and '"nbx_clumps: a local step awaits nbx_commit"' in ctx
-    assert len(re.findall(r"hipStreamSynchronize\(o->stream\)", src)) == 2  # one synchronisation, and the one of the failure path
-    assert len(re.findall(r"hipStreamSynchronize\(", src)) == 3  # and the ragged table's guard, which runs only when an exception leaves the call
-    assert len(re.findall(r"hipMemcpyAsync\(", src)) == 2 and len(re.findall(r"hipLaunchKernelGGL\(", src)) == 4  # an upload, a read-back; three kinds, one finish
+    # the read-back is the shared skeleton's: one use of the helper, and in the helper's body one copy, one synchronisation and
+    # the one of the failure path; the call's own source keeps the label upload and the ragged table's guard, which runs only when
+    # an exception leaves the call
+    assert len(re.findall(r"\bread_back\(", src)) == 1 and "hipStreamSynchronize(o->stream)" not in src
+    helper = shared[shared.index("int read_back("):]
+    helper = helper[:helper.index("\n}\n")]
+    assert len(re.findall(r"hipStreamSynchronize\(o->stream\)", helper)) == 2 and len(re.findall(r"hipStreamSynchronize\(", helper)) == 2
+    assert len(re.findall(r"hipStreamSynchronize\(", src)) == 1 and "~Drain() { if (armed) (void)hipStreamSynchronize(stream); }" in src
+    assert len(re.findall(r"hipMemcpyAsync\(", src)) == 1 and "hipMemcpyHostToDevice" in src  # an upload
+    assert len(re.findall(r"hipMemcpyAsync\(", helper)) == 1 and "hipMemcpyDeviceToHost" in helper  # a read-back
+    assert len(re.findall(r"hipLaunchKernelGGL\(", src)) == 4  # three kinds, one finish
 
 
 def test_python_methods_and_the_helpers_are_as_specified(nbx):
@@ -223,8 +234,11 @@ def test_the_kernels_live_in_their_own_translation_unit_reuse_the_shape_rule_and
     assert "__shared__ T4 ptile[kTile];" in kern and "__shared__ T4 vtile[kTile];" in kern  # two arrays per tile
     assert re.sub(r"//.*", "", kern).count("velm[j]") == 2 and re.sub(r"//.*", "", kern).count("lab[j]") == 2  # only below n
     assert "(float)l" not in both and "(T)l" not in both and "__int2float" not in both  # a label is never converted
-    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "device_alloc(", "device_table("):
+    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "ensure_bytes(", "ragged_member_table<", "ragged_extents(", "read_back("):
         assert fn in src, fn
+    shared = open(ANALYSIS).read()  # device_alloc and device_table are reached through ensure_bytes and ragged_member_table
+    for fn in ("device_alloc(", "device_table("):
+        assert fn in shared and fn not in re.sub(r"//.*", "", src), fn
     obj = open(os.path.join(CSRC, "nbx_object.hpp")).read()
     for field in ("clump_lab", "clump_part", "clump_out", "clump_tab"):
         assert re.search(r"void\* %s = nullptr;" % field, obj) and "o->%s" % field in obj[obj.index("inline void batch_release"):], field

@@ -28,6 +28,7 @@ from energy_ref import EPS2, gm_as_uploaded
 
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "nbx_field.hip")
+ANALYSIS = os.path.join(CSRC, "nbx_analysis.hpp")  # the host layer the analysis calls share
 OTHER_HEADERS = ("nbx.h", "nbx_diag.h", "nbx_ensemble.h", "nbx_ensemble_diag.h", "nbx_ragged.h", "nbx_ragged_diag.h", "nbx_batch_accel.h",
                  "nbx_kick.h", "nbx_timescale.h")
 ENTRY_POINTS = ("nbx_field", "nbx_ensemble_field", "nbx_ragged_field")
@@ -159,7 +160,7 @@ def test_the_build_files_compile_and_link_the_translation_unit():
     assert re.search(r"^\$\(PKG\)/libnbx\.so:.*\$\(PKG\)/nbx_field\.o", mk, re.M)
     rule = re.search(r"^\$\(PKG\)/nbx_field\.o: \$\(CSRC\)/nbx_field\.hip(.*)\n\t\$\(HIPCC\) \$\(HIPFLAGS\) -c \$< -o \$@$", mk, re.M)
     assert rule
-    for dep in ("nbx_field_kernels.hpp", "nbx_field_shape.hpp", "nbx_ensemble_internal.hpp", "nbx_ragged_internal.hpp", "nbx_internal.hpp",
+    for dep in ("nbx_field_kernels.hpp", "nbx_analysis.hpp", "nbx_field_shape.hpp", "nbx_ensemble_internal.hpp", "nbx_ragged_internal.hpp", "nbx_internal.hpp",
                 "nbx_batch.hpp", "nbx_object.hpp", "nbx_plan.hpp", "nbx_pair.hpp", "include/nbx_field.h", "include/nbx_ensemble.h",
                 "include/nbx_ragged.h"):
         assert dep in rule.group(1), dep
@@ -182,8 +183,10 @@ def test_the_kernels_live_in_their_own_translation_unit_and_the_shape_rule_inclu
     both = re.sub(r"//.*", "", open(SRC).read() + open(os.path.join(CSRC, "nbx_field_kernels.hpp")).read())
     assert "atomic" not in both
     src = open(SRC).read()
-    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "device_alloc("):
+    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "ensure_bytes(", "ragged_member_table<", "ragged_extents(", "read_back("):
         assert fn in src, fn
+    shared = open(ANALYSIS).read()  # device_alloc is reached through ensure_bytes
+    assert "device_alloc(" in shared and "device_alloc(" not in re.sub(r"//.*", "", src)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -28,6 +28,7 @@ from field_ref import field_shape
 
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "nbx_fof.hip")
+ANALYSIS = os.path.join(CSRC, "nbx_analysis.hpp")  # the host layer the analysis calls share
 KERNELS = "nbx_fof_kernels.hpp"
 OTHER_HEADERS = ("nbx.h", "nbx_diag.h", "nbx_ensemble.h", "nbx_ensemble_diag.h", "nbx_ragged.h", "nbx_ragged_diag.h", "nbx_batch_accel.h",
                  "nbx_kick.h", "nbx_timescale.h", "nbx_field.h", "nbx_neighbours.h", "nbx_paircount.h", "nbx_tracers.h", "nbx_knn.h")
@@ -158,8 +159,9 @@ def test_the_size_bound_the_pass_guard_and_their_texts_are_in_the_source():
     src = re.sub(r"//.*", "", open(SRC).read())
     hdr = re.sub(r"//.*", "", open(os.path.join(CSRC, KERNELS)).read())
     assert "constexpr long long kFofMaxBodies = kFieldMaxPoints;" in hdr and "constexpr int kFofNone = 0x7fffffff;" in hdr
-    assert '"nbx_fof: n exceeds 4194304"' in src and '"count * n exceeds"' in src and '"the bodies of the range exceed"' in src
-    assert "(long long)c->n > kFofMaxBodies" in src and "range_bodies(o, first, count) > kFofMaxBodies" in src
+    shared = re.sub(r"//.*", "", open(ANALYSIS).read())  # range_bodies and range_noun: one definition for every call
+    assert '"nbx_fof: n exceeds 4194304"' in src and '"count * n exceeds"' in shared and '"the bodies of the range exceed"' in shared
+    assert "(long long)c->n > kFofMaxBodies" in src and "range_bodies(o, first, count) > kFofMaxBodies" in src and "range_noun(o)" in src
     batch = src[src.index("int batch_fof("):]
     order = [batch.index(w) for w in ("is NULL", "bad_radius(", "check_range(", "kFofMaxBodies", "check_uploaded(", "no_output(a)", "use_device(")]
     assert order == sorted(order)
@@ -167,8 +169,10 @@ def test_the_size_bound_the_pass_guard_and_their_texts_are_in_the_source():
     order = [ctx.index(w) for w in ("is NULL", "bad_radius(", "kFofMaxBodies", "->uploaded", "pending_commit", "no_output(a)", "use_device(")]
     assert order == sorted(order)
     assert "if (passes > n_max) return fail(NBX_ERR_INTERNAL" in src and "did not settle in n + 1 passes" in src
-    # one synchronisation per pass, on a 4-byte word, and one for the results
+    # one synchronisation per pass, on a 4-byte word, and one for the results: the pass loop is the call's own flow, not the shared
+    # read-back skeleton
     assert len(re.findall(r"hipStreamSynchronize\(o->stream\)", src)) == 3 and "sizeof(int), hipMemcpyDeviceToHost" in src
+    assert "read_back(" not in src
 
 
 def test_python_methods_keys_and_the_helper_are_as_specified(nbx):
@@ -192,7 +196,7 @@ def test_the_build_files_compile_and_link_the_translation_unit():
     rule = re.search(r"^\$\(PKG\)/nbx_fof\.o: \$\(CSRC\)/nbx_fof\.hip(.*)\n\t\$\(HIPCC\) \$\(HIPFLAGS\) -c \$< -o \$@$", mk, re.M)
     knn = re.search(r"^\$\(PKG\)/nbx_knn\.o: \$\(CSRC\)/nbx_knn\.hip(.*)\n", mk, re.M)
     assert rule and rule.group(1) == knn.group(1).replace("knn", "fof")  # the same dependency list
-    for dep in (KERNELS, "nbx_field_shape.hpp", "nbx_ensemble_internal.hpp", "nbx_ragged_internal.hpp", "nbx_internal.hpp",
+    for dep in (KERNELS, "nbx_analysis.hpp", "nbx_field_shape.hpp", "nbx_ensemble_internal.hpp", "nbx_ragged_internal.hpp", "nbx_internal.hpp",
                 "nbx_batch.hpp", "nbx_object.hpp", "nbx_plan.hpp", "nbx_diag_shape.hpp", "nbx_pair.hpp", "include/nbx_fof.h",
                 "include/nbx_ensemble.h", "include/nbx_ragged.h", "include/nbx.h", "include/nbx_diag.h"):
         assert dep in rule.group(1), dep
@@ -221,8 +225,12 @@ def test_the_kernels_live_in_their_own_translation_unit_reuse_the_shape_rule_and
     assert len(re.findall(r"\batomic\w+\(", both)) == 5 and both.count("atomicMin(") == 2
     body = kern[kern.index("void fof_body("):kern.index("struct FofRange")]
     assert "atomic" not in re.sub(r"//.*", "", body) and "posm" not in re.sub(r"//.*", "", body)  # the pair work reads the staged records alone
-    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "device_alloc(", "device_table("):
+    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "ensure_bytes(", "ragged_member_table<", "ragged_extents("):
         assert fn in src, fn
+    shared = open(ANALYSIS).read()  # device_alloc and device_table are reached through ensure_bytes and ragged_member_table
+    for fn in ("device_alloc(", "device_table("):
+        assert fn in shared and fn not in re.sub(r"//.*", "", src), fn
+    assert "rec_off += (unsigned long long)padded(mem.n);" in src  # the staged records' offset is accumulated in this call's own maker
     obj = open(os.path.join(CSRC, "nbx_object.hpp")).read()
     for field in ("fof_rec", "fof_part", "fof_work", "fof_out", "fof_tab"):
         assert re.search(r"void\* %s = nullptr;" % field, obj) and "o->%s" % field in obj[obj.index("inline void batch_release"):], field

@@ -18,6 +18,7 @@ from conftest import ROOT, PKG
 
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "nbx_hermite.hip")
+ANALYSIS = os.path.join(CSRC, "nbx_analysis.hpp")  # the host layer the analysis calls share
 KERNELS = "nbx_hermite_kernels.hpp"
 ENTRY_POINTS = ("nbx_hermite_step", "nbx_ensemble_hermite_step", "nbx_ragged_hermite_step")
 NOUN = {"nbx_hermite_step": "ctx", "nbx_ensemble_hermite_step": "ensemble", "nbx_ragged_hermite_step": "ragged ensemble"}
@@ -145,6 +146,10 @@ def test_the_checks_are_in_the_source_in_the_headers_order_and_the_call_neither_
     assert order == sorted(order)
     assert "hipStreamSynchronize" not in src and "hipDeviceSynchronize" not in src and "DeviceToHost" not in src
     assert "hipMemcpy" not in src  # the one copy, of the ragged member table, is device_table's, from bytes that live with the object
+    shared = re.sub(r"//.*", "", open(ANALYSIS).read())  # which ragged_member_table reaches; the size bound's words are shared too
+    assert "&r->herm_tab, &r->herm_tab_src" in src and "device_table(" in shared and "device_table(" not in src
+    assert '"members * n exceeds"' in shared and '"the bodies of the members exceed"' in shared
+    assert "object_bodies(o) > kHermiteMaxBodies" in src and "bodies_noun(o)" in src and '"nbx_hermite_step: n exceeds 4194304"' in src
     assert "timed_launch" not in src and "steps_done +=" not in src and "cur ^=" not in src
     assert len(re.findall(r"hipLaunchKernelGGL\(", src)) == 4  # three kinds, one finish
     obj = open(os.path.join(CSRC, "nbx_object.hpp")).read()

@@ -30,6 +30,7 @@ from energy_ref import EPS2
 
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "nbx_jerk.hip")
+ANALYSIS = os.path.join(CSRC, "nbx_analysis.hpp")  # the host layer the analysis calls share
 KERNELS = "nbx_jerk_kernels.hpp"
 ENTRY_POINTS = ("nbx_jerk", "nbx_ensemble_jerk", "nbx_ragged_jerk")
 NOUN = {"nbx_jerk": "ctx", "nbx_ensemble_jerk": "ensemble", "nbx_ragged_jerk": "ragged ensemble"}
@@ -169,7 +170,9 @@ def test_the_size_bound_and_the_refusals_are_in_the_source_in_the_stated_order()
     src = re.sub(r"//.*", "", open(SRC).read())
     hdr = re.sub(r"//.*", "", open(os.path.join(CSRC, KERNELS)).read())
     assert "constexpr long long kJerkMaxBodies = kFieldMaxPoints;" in hdr
-    assert '"nbx_jerk: n exceeds 4194304"' in src and '"count * n exceeds"' in src and '"the bodies of the range exceed"' in src
+    shared = re.sub(r"//.*", "", open(ANALYSIS).read())  # range_bodies and range_noun: one definition for every call
+    assert '"nbx_jerk: n exceeds 4194304"' in src and '"count * n exceeds"' in shared and '"the bodies of the range exceed"' in shared
+    assert "(long long)c->n > kJerkMaxBodies" in src and "range_bodies(o, first, count) > kJerkMaxBodies" in src and "range_noun(o)" in src
     batch = src[src.index("int batch_jerk("):]
     order = [batch.index(w) for w in ("is NULL", "out is NULL", "check_range(", "kJerkMaxBodies", "check_uploaded(", "no_output(*out)", "use_device(")]
     assert order == sorted(order)
@@ -179,8 +182,14 @@ def test_the_size_bound_and_the_refusals_are_in_the_source_in_the_stated_order()
     assert order == sorted(order)
     text = "the context owns a slice of the bodies (the velocities of the others are not resident)"
     assert 'fail(NBX_ERR_STATE, "nbx_jerk: %s")' % text in ctx and '"nbx_jerk: a local step awaits nbx_commit"' in ctx
-    assert len(re.findall(r"hipStreamSynchronize\(o->stream\)", src)) == 2  # one synchronisation, and the one of the failure path
-    assert len(re.findall(r"hipMemcpyAsync\(", src)) == 1 and len(re.findall(r"hipLaunchKernelGGL\(", src)) == 4  # one read-back; three kinds, one finish
+    # the read-back is the shared skeleton's: no synchronisation and no copy of the call's own, one use of the helper, and in the
+    # helper's body one copy, one synchronisation and the one of the failure path
+    assert "hipStreamSynchronize" not in src and "hipMemcpy" not in src and len(re.findall(r"\bread_back\(", src)) == 1
+    helper = shared[shared.index("int read_back("):]
+    helper = helper[:helper.index("\n}\n")]
+    assert len(re.findall(r"hipStreamSynchronize\(o->stream\)", helper)) == 2 and len(re.findall(r"hipStreamSynchronize\(", helper)) == 2
+    assert len(re.findall(r"hipMemcpyAsync\(", helper)) == 1 and "hipMemcpyDeviceToHost" in helper  # one read-back
+    assert len(re.findall(r"hipLaunchKernelGGL\(", src)) == 4  # three kinds, one finish
 
 
 class _Fake:
@@ -243,8 +252,11 @@ def test_the_kernels_live_in_their_own_translation_unit_reuse_the_shape_rule_and
     code = re.sub(r"//.*", "", kern)
     assert code.count("velm[j]") == 2 and len(re.findall(r"if \(j < n\) next_v = velm\[j\];", code)) == 2  # only below n
     assert code.count("velm[li]") == 1 and "if (li < n) {\n      p = posm[li];\n      v = velm[li];" in code
-    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "device_alloc(", "device_table("):
+    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "ensure_bytes(", "ragged_member_table<", "ragged_extents(", "read_back("):
         assert fn in src, fn
+    shared = open(ANALYSIS).read()  # device_alloc and device_table are reached through ensure_bytes and ragged_member_table
+    for fn in ("device_alloc(", "device_table("):
+        assert fn in shared and fn not in re.sub(r"//.*", "", src), fn
     obj = open(os.path.join(CSRC, "nbx_object.hpp")).read()
     for field in ("jerk_part", "jerk_out", "jerk_tab"):
         assert re.search(r"void\* %s = nullptr;" % field, obj) and "o->%s" % field in obj[obj.index("inline void batch_release"):], field

@@ -27,6 +27,7 @@ from field_ref import field_shape
 
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "nbx_knn.hip")
+ANALYSIS = os.path.join(CSRC, "nbx_analysis.hpp")  # the host layer the analysis calls share
 KERNELS = "nbx_knn_kernels.hpp"
 OTHER_HEADERS = ("nbx.h", "nbx_diag.h", "nbx_ensemble.h", "nbx_ensemble_diag.h", "nbx_ragged.h", "nbx_ragged_diag.h", "nbx_batch_accel.h",
                  "nbx_kick.h", "nbx_timescale.h", "nbx_field.h", "nbx_neighbours.h", "nbx_paircount.h", "nbx_tracers.h")
@@ -161,6 +162,8 @@ def test_the_size_bound_is_the_fields_scaled_by_k_and_its_texts_are_in_the_sourc
     assert "kKnnMax == NBX_KNN_MAX" in src
     assert '"nbx_knn: n * k exceeds 4194304"' in src and '"count * n * k exceeds"' in src and '"the bodies of the range times k exceed"' in src
     assert "(long long)c->n * (long long)k > kKnnMaxEntries" in src and "range_bodies(o, first, count) * (long long)k > kKnnMaxEntries" in src
+    shared = re.sub(r"//.*", "", open(ANALYSIS).read())  # range_bodies is the shared one; the two nouns above are this call's own
+    assert "long long range_bodies(" in shared and "long long range_bodies(" not in src and "entries_noun(o)" in src
     batch = src[src.index("int batch_knn("):]
     order = [batch.index(w) for w in ("is NULL", "bad_k(", "check_range(", "kKnnMaxEntries", "check_uploaded(", "no_output(a)", "use_device(")]
     assert order == sorted(order)
@@ -190,7 +193,7 @@ def test_the_build_files_compile_and_link_the_translation_unit():
     assert re.search(r"^\$\(PKG\)/libnbx\.so:.*\$\(PKG\)/nbx_knn\.o", mk, re.M)
     rule = re.search(r"^\$\(PKG\)/nbx_knn\.o: \$\(CSRC\)/nbx_knn\.hip(.*)\n\t\$\(HIPCC\) \$\(HIPFLAGS\) -c \$< -o \$@$", mk, re.M)
     assert rule
-    for dep in (KERNELS, "nbx_field_shape.hpp", "nbx_ensemble_internal.hpp", "nbx_ragged_internal.hpp", "nbx_internal.hpp",
+    for dep in (KERNELS, "nbx_analysis.hpp", "nbx_field_shape.hpp", "nbx_ensemble_internal.hpp", "nbx_ragged_internal.hpp", "nbx_internal.hpp",
                 "nbx_batch.hpp", "nbx_object.hpp", "nbx_plan.hpp", "nbx_diag_shape.hpp", "nbx_pair.hpp", "include/nbx_knn.h",
                 "include/nbx_ensemble.h", "include/nbx_ragged.h", "include/nbx.h", "include/nbx_diag.h"):
         assert dep in rule.group(1), dep
@@ -217,8 +220,11 @@ def test_the_kernels_live_in_their_own_translation_unit_reuse_the_shape_rule_and
     assert "diag_splits" not in both and not re.search(r"constexpr\s+\w+\s+\w*shape\w*\s*\(", both)
     assert "fmaT(dx, dx, fmaT(dy, dy, fmaT(dz, dz, softening2<T>())))" in kern  # r2 restated, not shared
     assert "__any(" in kern  # the wave-uniform branch around the insertion
-    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "device_alloc(", "device_table("):
+    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "ensure_bytes(", "ragged_member_table<", "ragged_extents(", "read_back("):
         assert fn in src, fn
+    shared = open(ANALYSIS).read()  # device_alloc and device_table are reached through ensure_bytes and ragged_member_table
+    for fn in ("device_alloc(", "device_table("):
+        assert fn in shared and fn not in re.sub(r"//.*", "", src), fn
     obj = open(os.path.join(CSRC, "nbx_object.hpp")).read()
     for field in ("knn_part", "knn_out", "knn_tab"):
         assert re.search(r"void\* %s = nullptr;" % field, obj) and "o->%s" % field in obj[obj.index("inline void batch_release"):], field

@@ -26,6 +26,7 @@ from energy_ref import EPS2
 
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "nbx_neighbours.hip")
+ANALYSIS = os.path.join(CSRC, "nbx_analysis.hpp")  # the host layer the analysis calls share
 KERNELS = "nbx_neighbours_kernels.hpp"
 OTHER_HEADERS = ("nbx.h", "nbx_diag.h", "nbx_ensemble.h", "nbx_ensemble_diag.h", "nbx_ragged.h", "nbx_ragged_diag.h", "nbx_batch_accel.h",
                  "nbx_kick.h", "nbx_timescale.h", "nbx_field.h")
@@ -142,7 +143,9 @@ def test_the_size_bound_is_the_fields_and_its_texts_are_in_the_source():
     src = re.sub(r"//.*", "", open(SRC).read())
     hdr = re.sub(r"//.*", "", open(os.path.join(CSRC, KERNELS)).read())
     assert "constexpr long long kNbMaxBodies = kFieldMaxPoints;" in hdr
-    assert '"nbx_neighbours: n exceeds 4194304"' in src and '"count * n exceeds"' in src and '"the bodies of the range exceed"' in src
+    shared = re.sub(r"//.*", "", open(ANALYSIS).read())  # range_bodies and range_noun: one definition for every call
+    assert '"nbx_neighbours: n exceeds 4194304"' in src and '"count * n exceeds"' in shared and '"the bodies of the range exceed"' in shared
+    assert "(long long)c->n > kNbMaxBodies" in src and "range_bodies(o, first, count) > kNbMaxBodies" in src and "range_noun(o)" in src
     batch = src[src.index("int batch_neighbours("):]
     order = [batch.index(w) for w in ("is NULL", "bad_radius(", "check_range(", "kNbMaxBodies", "check_uploaded(", "no_output(a)", "use_device(")]
     assert order == sorted(order)
@@ -173,7 +176,7 @@ def test_the_build_files_compile_and_link_the_translation_unit():
     assert re.search(r"^\$\(PKG\)/libnbx\.so:.*\$\(PKG\)/nbx_neighbours\.o", mk, re.M)
     rule = re.search(r"^\$\(PKG\)/nbx_neighbours\.o: \$\(CSRC\)/nbx_neighbours\.hip(.*)\n\t\$\(HIPCC\) \$\(HIPFLAGS\) -c \$< -o \$@$", mk, re.M)
     assert rule
-    for dep in (KERNELS, "nbx_field_shape.hpp", "nbx_ensemble_internal.hpp", "nbx_ragged_internal.hpp", "nbx_internal.hpp",
+    for dep in (KERNELS, "nbx_analysis.hpp", "nbx_field_shape.hpp", "nbx_ensemble_internal.hpp", "nbx_ragged_internal.hpp", "nbx_internal.hpp",
                 "nbx_batch.hpp", "nbx_object.hpp", "nbx_plan.hpp", "nbx_diag_shape.hpp", "nbx_pair.hpp", "include/nbx_neighbours.h",
                 "include/nbx_ensemble.h", "include/nbx_ragged.h", "include/nbx.h", "include/nbx_diag.h"):
         assert dep in rule.group(1), dep
@@ -195,8 +198,11 @@ def test_the_kernels_live_in_their_own_translation_unit_and_reuse_the_shape_rule
     assert "atomic" not in both
     assert "field_shape(" in both and '#include "nbx_field_shape.hpp"' in kern  # the field's rule, no new one
     assert "diag_splits" not in both and not re.search(r"constexpr\s+\w+\s+\w*shape\w*\s*\(", both)
-    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "device_alloc(", "device_table("):
+    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "ensure_bytes(", "ragged_member_table<", "ragged_extents(", "read_back("):
         assert fn in src, fn
+    shared = open(ANALYSIS).read()  # device_alloc and device_table are reached through ensure_bytes and ragged_member_table
+    for fn in ("device_alloc(", "device_table("):
+        assert fn in shared and fn not in re.sub(r"//.*", "", src), fn
     obj = open(os.path.join(CSRC, "nbx_object.hpp")).read()
     for field in ("nb_part", "nb_out", "nb_tab"):
         assert re.search(r"void\* %s = nullptr;" % field, obj) and "o->%s" % field in obj[obj.index("inline void batch_release"):], field

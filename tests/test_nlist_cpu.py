@@ -18,6 +18,7 @@ from energy_ref import EPS2
 
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "nbx_nlist.hip")
+ANALYSIS = os.path.join(CSRC, "nbx_analysis.hpp")  # the host layer the analysis calls share
 KERNELS = "nbx_nlist_kernels.hpp"
 SHAPE = "nbx_nlist_shape.hpp"
 ENTRY_POINTS = ("nbx_nlist", "nbx_ensemble_nlist", "nbx_ragged_nlist")
@@ -175,7 +176,9 @@ def test_the_bounds_and_the_order_of_the_checks_are_in_the_source():
     src = re.sub(r"//.*", "", open(SRC).read())
     shape = re.sub(r"//.*", "", open(os.path.join(CSRC, SHAPE)).read())
     assert "constexpr long long kNlMaxBodies = 1ll << 22;" in shape and "constexpr long long kNlMaxCapacity = 1ll << 28;" in shape
-    assert '"nbx_nlist: n exceeds 4194304"' in src and '"count * n exceeds"' in src and '"the bodies of the range exceed"' in src
+    shared = re.sub(r"//.*", "", open(ANALYSIS).read())  # range_bodies and range_noun: one definition for every call
+    assert '"nbx_nlist: n exceeds 4194304"' in src and '"count * n exceeds"' in shared and '"the bodies of the range exceed"' in shared
+    assert "(long long)c->n > kNlMaxBodies" in src and "range_bodies(o, first, count) > kNlMaxBodies" in src and "range_noun(o)" in src
     batch = src[src.index("int batch_nlist("):]
     order = [batch.index(w) for w in ("is NULL", "check_args(", "check_range(", "kNlMaxBodies", "check_uploaded(", "count == 0", "use_device(")]
     assert order == sorted(order)
@@ -269,8 +272,12 @@ def test_the_kernels_live_in_their_own_translation_unit_reuse_the_shape_rule_and
     assert both.count("r2 <= h2") == 1 and both.count("nl_in<") == 3
     assert "if (__any(in0 || in1)) {" in kern and "if (__any(some)) {" in kern and "if (pos < end) {" in kern
     assert kern.count("out.index[") == 1 and kern.count("out.r2[") == 1
-    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "device_alloc(", "device_table("):
+    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "ensure_bytes(", "ragged_member_table<", "ragged_extents("):
         assert fn in src, fn
+    shared = open(os.path.join(CSRC, "nbx_analysis.hpp")).read()  # device_alloc and device_table are reached through the two helpers
+    for fn in ("device_alloc(", "device_table("):
+        assert fn in shared and fn not in re.sub(r"//.*", "", src), fn
+    assert "read_back(" not in src  # the scan and the two lists are the call's own flow, not the shared read-back skeleton
     obj = open(os.path.join(CSRC, "nbx_object.hpp")).read()
     for field in ("nl_seg", "nl_scan", "nl_index", "nl_r2", "nl_tab"):
         assert re.search(r"void\* %s = nullptr;" % field, obj) and "o->%s" % field in obj[obj.index("inline void batch_release"):], field

@@ -21,6 +21,7 @@ from conftest import ROOT, PKG
 
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "nbx_paircount.hip")
+ANALYSIS = os.path.join(CSRC, "nbx_analysis.hpp")  # the host layer the analysis calls share
 ENTRY_POINTS = ("nbx_paircount", "nbx_ensemble_paircount", "nbx_ragged_paircount")
 NOUN = {"nbx_paircount": "ctx", "nbx_ensemble_paircount": "ensemble", "nbx_ragged_paircount": "ragged ensemble"}
 
@@ -239,7 +240,9 @@ def test_the_size_bound_and_the_order_of_the_checks_are_in_the_source():
     src = re.sub(r"//.*", "", open(SRC).read())
     hdr = re.sub(r"//.*", "", open(os.path.join(CSRC, "nbx_paircount_kernels.hpp")).read())
     assert "constexpr long long kPcMaxBodies = kFieldMaxPoints;" in hdr and "atomic" not in src + hdr
-    assert '"nbx_paircount: n exceeds 4194304"' in src and '"count * n exceeds"' in src and '"the bodies of the range exceed"' in src
+    shared = re.sub(r"//.*", "", open(ANALYSIS).read())  # range_bodies and range_noun: one definition for every call
+    assert '"nbx_paircount: n exceeds 4194304"' in src and '"count * n exceeds"' in shared and '"the bodies of the range exceed"' in shared
+    assert "(long long)c->n > kPcMaxBodies" in src and "range_bodies(o, first, count) > kPcMaxBodies" in src and "range_noun(o)" in src
     batch = src[src.index("int batch_paircount("):]
     order = [batch.index(w) for w in ("is NULL", "check_radii(", "check_range(", "kPcMaxBodies", "check_uploaded(", "!counts", "use_device(")]
     assert order == sorted(order)

@@ -31,6 +31,7 @@ from energy_ref import EPS2, gm_as_uploaded
 
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "nbx_tidal.hip")
+ANALYSIS = os.path.join(CSRC, "nbx_analysis.hpp")  # the host layer the analysis calls share
 KERNELS = "nbx_tidal_kernels.hpp"
 POINT_ENTRIES = ("nbx_tidal", "nbx_ensemble_tidal", "nbx_ragged_tidal")
 BODY_ENTRIES = ("nbx_tidal_bodies", "nbx_ensemble_tidal_bodies", "nbx_ragged_tidal_bodies")
@@ -306,7 +307,7 @@ def test_the_build_files_compile_and_link_the_translation_unit():
     assert re.search(r"^\$\(PKG\)/libnbx\.so:.*\$\(PKG\)/nbx_tidal\.o", mk, re.M)
     rule = re.search(r"^\$\(PKG\)/nbx_tidal\.o: \$\(CSRC\)/nbx_tidal\.hip(.*)\n\t\$\(HIPCC\) \$\(HIPFLAGS\) -c \$< -o \$@$", mk, re.M)
     assert rule
-    for dep in (KERNELS, "nbx_field_shape.hpp", "nbx_ensemble_internal.hpp", "nbx_ragged_internal.hpp", "nbx_internal.hpp",
+    for dep in (KERNELS, "nbx_analysis.hpp", "nbx_field_shape.hpp", "nbx_ensemble_internal.hpp", "nbx_ragged_internal.hpp", "nbx_internal.hpp",
                 "nbx_batch.hpp", "nbx_object.hpp", "nbx_plan.hpp", "nbx_pair.hpp", "include/nbx_tidal.h", "include/nbx_ensemble.h",
                 "include/nbx_ragged.h"):
         assert dep in rule.group(1), dep
@@ -327,8 +328,14 @@ def test_the_kernels_live_in_their_own_translation_unit_and_use_the_fields_shape
     assert "atomic" not in kern + re.sub(r"//.*", "", src)
     assert '#include "nbx_field_shape.hpp"' in kern and "field_shape(" in kern and "field_shape(pts, c->n)" in src
     assert "kTidalMaxPoints = kFieldMaxPoints / 2" in kern
-    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "device_alloc(", "device_table("):
+    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "ensure_bytes(", "ragged_member_table<", "ragged_extents(", "read_back("):
         assert fn in src, fn
+    shared = open(ANALYSIS).read()  # device_alloc and device_table are reached through ensure_bytes and ragged_member_table
+    for fn in ("device_alloc(", "device_table("):
+        assert fn in shared and fn not in re.sub(r"//.*", "", src), fn
+    # the bodies-mode size bound's words are the shared ones
+    assert '"count * n exceeds"' in shared and '"the bodies of the range exceed"' in shared
+    assert "range_bodies(o, first, count) > kTidalMaxPoints" in src and "range_noun(o)" in src
     obj = open(os.path.join(CSRC, "nbx_object.hpp")).read()
     for field in ("tidal_pts", "tidal_part", "tidal_out", "tidal_tab"):
         assert re.search(r"void\* %s = nullptr;" % field, obj) and "o->%s" % field in obj[obj.index("inline void batch_release"):], field

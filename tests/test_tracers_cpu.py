@@ -22,6 +22,7 @@ from conftest import ROOT, PKG
 
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "nbx_tracers.hip")
+ANALYSIS = os.path.join(CSRC, "nbx_analysis.hpp")  # the host layer the analysis calls share
 KINDS = (("nbx", "nbx_ctx", "ctx"), ("nbx_ensemble", "nbx_ensemble", "ensemble"), ("nbx_ragged", "nbx_ragged", "ragged ensemble"))
 WORDS = ("upload", "download", "count", "step", "kick")
 OTHER_HEADERS = ("nbx.h", "nbx_diag.h", "nbx_ensemble.h", "nbx_ensemble_diag.h", "nbx_ragged.h", "nbx_ragged_diag.h", "nbx_batch_accel.h",
@@ -205,7 +206,7 @@ def test_the_build_files_compile_and_link_the_translation_unit():
     assert re.search(r"^\$\(PKG\)/libnbx\.so:.*\$\(PKG\)/nbx_tracers\.o", mk, re.M)
     rule = re.search(r"^\$\(PKG\)/nbx_tracers\.o: \$\(CSRC\)/nbx_tracers\.hip(.*)\n\t\$\(HIPCC\) \$\(HIPFLAGS\) -c \$< -o \$@$", mk, re.M)
     assert rule
-    for dep in ("nbx_tracers_kernels.hpp", "nbx_field_shape.hpp", "nbx_ensemble_internal.hpp", "nbx_ragged_internal.hpp", "nbx_internal.hpp",
+    for dep in ("nbx_tracers_kernels.hpp", "nbx_analysis.hpp", "nbx_field_shape.hpp", "nbx_ensemble_internal.hpp", "nbx_ragged_internal.hpp", "nbx_internal.hpp",
                 "nbx_batch.hpp", "nbx_object.hpp", "nbx_plan.hpp", "nbx_pair.hpp", "include/nbx_tracers.h", "include/nbx_ensemble.h",
                 "include/nbx_ragged.h"):
         assert dep in rule.group(1), dep
@@ -231,8 +232,11 @@ def test_the_kernels_live_in_their_own_translation_unit_and_the_body_step_goes_t
     api = open(os.path.join(CSRC, "nbx_api.hip")).read()
     hook = api[api.index("int nbx_detail::enqueue_one_step("):]
     assert "enqueue_step_any(c, dt)" in hook[:hook.index("\n}\n")] and "c->cur ^= 1;" in hook[:hook.index("\n}\n")]
-    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "device_alloc(", "device_table("):
+    for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "ensure_bytes(", "ragged_member_table<"):
         assert fn in src, fn
+    shared = open(ANALYSIS).read()  # device_alloc and device_table are reached through ensure_bytes and ragged_member_table
+    for fn in ("device_alloc(", "device_table("):
+        assert fn in shared and fn not in src, fn
     obj = open(os.path.join(CSRC, "nbx_object.hpp")).read()
     for field in ("tr_pos", "tr_vel", "tr_part", "tr_tab"):
         assert re.search(r"void\* %s = nullptr;" % field, obj) and "o->%s" % field in obj[obj.index("inline void batch_release"):], field
