@@ -11,7 +11,10 @@ q = min_i s_i, a NaN never selected.  The quantiser, integers only: E = the expo
 k_crit = floor(E / 2); after a step of 2^k: k + 1 if k_crit > k and t is a multiple of 2^(k+1), else k if k_crit >= k, else
 k_crit; at the start k_crit; clamped to [k_cap - levels, k_cap], a step the clamp raised counting as a floor step once taken.
 
-FAULTS can be planted; tests/test_advance_cpu.py shows that each changes a recorded history or an end state."""
+FAULTS can be planted; tests/test_advance_cpu.py shows that each changes a recorded history or an end state.  FLOOR_FAULTS sit in the
+clamp, the floor count and the start rule where J is 0: they change nothing where the floor never binds and no body is at rest --
+every case of that module -- and tests/test_large_steppers_cpu.py shows that each changes a clock of the clamp and cold-start cases
+of tests/test_advance_gpu.py."""
 import math
 
 import numpy as np
@@ -21,6 +24,8 @@ import hermite_ref as H
 TILE = 256
 FAULTS = ("a2 is not advanced to the end of the step", "the factor 12 in a3", "doubling without the commensurability test",
           "E / 2 rounded towards zero", "the start rule on every step", "the minimum over padding records")
+FLOOR_FAULTS = ("floor_steps counts a step when it is chosen", "raised is evaluated after the clamp",
+                "a done system's floor_steps keeps counting", "the start candidate is 0 where J is 0")
 
 
 def exponent(x):
@@ -32,12 +37,12 @@ def _norm2(v):
     return (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]
 
 
-def start_candidates(a, j):
+def start_candidates(a, j, fault=None):
     """(n,) candidates after the evaluation that starts a call: A / J where J > 0, else +inf."""
     a, j = (np.asarray(x).astype(np.float64) for x in (a, j))
     A, J = _norm2(a), _norm2(j)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        return np.where(J > 0.0, A / J, np.inf)
+        return np.where(J > 0.0, A / J, 0.0 if fault == "the start candidate is 0 where J is 0" else np.inf)
 
 
 def candidates(a0, j0, a1, j1, h, fault=None):
@@ -84,7 +89,8 @@ def choose(q, eta2, k_cap, levels, k=None, t=None, fault=None):
         fits = u == math.floor(u) or fault == "doubling without the commensurability test"
         nxt = k + 1 if (kc > k and fits) else k
     k_floor = k_cap - levels
-    return min(max(nxt, k_floor), k_cap), nxt < k_floor
+    clamped = min(max(nxt, k_floor), k_cap)
+    return clamped, (clamped if fault == "raised is evaluated after the clamp" else nxt) < k_floor
 
 
 def new_clock():
@@ -93,9 +99,11 @@ def new_clock():
 
 def start(clock, a, j, eta, k_cap, levels, fault=None):
     """The clock after the evaluation (a, j) that starts a call without resume."""
-    k, raised = choose(minimum(start_candidates(a, j), fault), float(eta) * float(eta), k_cap, levels, fault=fault)
+    k, raised = choose(minimum(start_candidates(a, j, fault), fault), float(eta) * float(eta), k_cap, levels, fault=fault)
     clock.update(new_clock())
     clock.update(dt_next=2.0 ** k, floor_next=raised)
+    if fault == "floor_steps counts a step when it is chosen":
+        clock.update(floor_steps=int(raised))
     return clock
 
 
@@ -108,8 +116,8 @@ def after_step(clock, a0, j0, a1, j1, eta, k_cap, levels, fault=None):
         assert t - h == clock["t"] and (t / h) == math.floor(t / h)  # t += h is exact and t stays a multiple of h
     q = minimum(candidates(a0, j0, a1, j1, h, fault), fault)
     nk, raised = choose(q, float(eta) * float(eta), k_cap, levels, k, t, fault)
-    clock.update(t=t, dt_last=h, dt_next=2.0 ** nk, steps=clock["steps"] + 1, floor_steps=clock["floor_steps"] + int(clock["floor_next"]),
-                 floor_next=raised)
+    counted = raised if fault == "floor_steps counts a step when it is chosen" else clock["floor_next"]
+    clock.update(t=t, dt_last=h, dt_next=2.0 ** nk, steps=clock["steps"] + 1, floor_steps=clock["floor_steps"] + int(counted), floor_next=raised)
     return clock, q
 
 
@@ -125,7 +133,7 @@ def public(clock, t_end, n=None):
 def run(state, precision, t_end, k_cap, levels, eta, max_steps, evaluate, fault=None, clock=None, carry=None):
     """Up to max_steps steps of one system towards t_end.  clock, carry: what a previous run left (None: t = 0 and an evaluation
     at `state`).  Returns {"state", "carry": (a, j), "clock", "history": [(t before the step, h, eta2 * q after it), ...]}."""
-    assert fault is None or fault in FAULTS, fault
+    assert fault is None or fault in FAULTS + FLOOR_FAULTS, fault
     T = H.DTYPE[precision]
     mass = np.asarray(state["mass"], dtype=T)
     x, v = H.unpack(state, T)
@@ -139,6 +147,9 @@ def run(state, precision, t_end, k_cap, levels, eta, max_steps, evaluate, fault=
     history = []
     for _ in range(max_steps):
         if clock["t"] >= t_end:
+            if fault == "a done system's floor_steps keeps counting":  # the launches of the steps a done system does not take
+                clock["floor_steps"] += int(clock["floor_next"])
+                continue
             break
         h = clock["dt_next"]
         k = H.consts(h, precision)

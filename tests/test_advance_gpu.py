@@ -13,7 +13,15 @@ clustered), 513 (a second column of one body), 2049 (five columns, two splits; c
 columns, four splits, the last one short), an ensemble of 3 x 2049 and a ragged ensemble of (5, 2049, 257, 1, 513).
 
 The chosen step depends on the last bit of a candidate only where eta^2 q sits on a power of four; the tests check, on the
-restatement's values alone, that every case stays 1e-9 (relative) away from one wherever the choice is not decided by the clamp."""
+restatement's values alone, that every case stays 1e-9 (relative) away from one wherever the choice is not decided by the clamp.
+
+The clamp and the degenerate candidates, in the second half of this module, all with dt_cap = 2^-4 and eta = 0.125, bit for bit
+against advance_ref.run fed by the device's evaluations: floors that bind (levels = 0, 2, 3, 8; floor_steps counted once the step
+is taken, across a resumed call, per member, kept by a member that is done while others go on), systems at rest (every start
+candidate +inf, dt_cap first, then a drop of several levels at once), +inf candidates beside finite ones (a massless body's
+partner; a coincident pair), and a member whose candidates are all NaN or +inf.  tests/test_large_steppers_cpu.py shows on the CPU
+which planted faults these cases see that the ones above do not.  The shapes above n = 4097 -- 15 splits, 2076 tiles, 1025
+clocks, a minimum decided by the last candidate of 531 441 -- live in tests/test_large_steppers_gpu.py."""
 import math
 import os
 import sys
@@ -269,6 +277,227 @@ def test_the_same_call_gives_the_same_bits_and_analysis_calls_between_resumed_ca
         r.diagnostics()
         _adv(r, max_steps=CALLS - 3, resume=True)
         assert H.same(r.download()[0], want[0]) and r.clock()[0] == want[1], precision
+
+
+# ---- the clamp, the cold start, candidates that are not finite ---------------------------------------------------------------------
+# (n, family, levels, steps, the exponents of the steps, floor_steps after them): jerk_ref.direct gives these histories in both
+# precisions with every x at least 0.012 from a power of four (tests/test_large_steppers_cpu.py); here they are asserted on the
+# restatement fed by the device's own evaluations, and the device's clock against that.
+FLOOR_CASES = ((5, "cloud", 2, 8, [-6] * 8, 7), (5, "cloud", 3, 16, [-6] + [-7] * 15, 13), (5, "cloud", 0, 3, [-4] * 3, 3),
+               (257, "clustered", 8, 6, [-12] * 6, 6))
+FLOOR_LEVELS = 3  # of the member cases
+FLOOR_ENSEMBLE = ((5, "cloud"), (5, "clustered"))
+FLOOR_RAGGED = ((5, "cloud"), (257, "clustered"), (1, "cloud"))
+FLOOR_MAX_STEPS = 12  # more than the 8 steps of 2^-7 that reach dt_cap: the launches of the last ones find members that are done
+COLD_SIZES = (5, 257, 2049)
+COLD_RAGGED = ((5, "rest"), (257, "cloud"), (257, "rest"))
+_solo = {}
+
+
+def degenerate_states(precision):
+    """{name: state}.  massless: two bodies, body 0 without mass -- body 1 feels nothing, a = j = 0, its candidate +inf at the
+    start and after every step (a zero denominator), body 0 decides.  coincident: three bodies, 0 and 1 at one position with one
+    velocity -- the softening keeps every value finite.  coincident massless: the same with body 2 without mass -- the pair feels
+    nothing (d = 0, u = 0 between its two), so two candidates are +inf and body 2 decides."""
+    two = R.make_state(precision, 2, "cloud")
+    two["mass"][0] = 0
+    three = R.make_state(precision, 3, "cloud")
+    for f in H.POS + H.VEL:
+        three[f][1] = three[f][0]
+    light = {k: v.copy() for k, v in three.items()}
+    light["mass"][2] = 0
+    return {"massless": two, "coincident": three, "coincident massless": light}
+
+
+def _check_every_x(history):
+    for _, _, x in history:
+        assert not (math.isfinite(x) and x > 0.0) or A.boundary_distance(x) >= 1e-9, x
+
+
+def solo(nbx, precision, name, state, levels, max_steps, t_end=FAR, first=None):
+    """A context holding `state` after advance(t_end, levels, max_steps) -- as one call, or as a call of `first` steps and a resumed
+    one of the rest -- beside the restatement fed by the device's own evaluations on a second context.  Asserts that clock and
+    state are the restatement's after every call; returns {"state", "clock", "ref", "start"}, start the restatement's start
+    candidates.  Computed once."""
+    key = (precision, name, levels, max_steps, t_end, first)
+    if key in _solo:
+        return _solo[key]
+    n = len(state["mass"])
+    with nbx.Context(n, precision) as a, nbx.Context(n, precision) as b:
+        ev = H.device_evaluate(b)
+        start = A.start_candidates(*ev(state))
+        a.upload(state)
+        parts = [max_steps] if first is None else [first, max_steps - first]
+        ref, history = None, []
+        for call, steps in enumerate(parts):
+            _adv(a, t_end, steps, resume=call > 0, levels=levels)
+            ref = A.run(state if ref is None else ref["state"], precision, t_end, K_CAP, levels, ETA, steps, ev,
+                        clock=ref and ref["clock"], carry=ref and ref["carry"])
+            history += ref["history"]
+            got, clock = a.download(), a.clock()
+            assert {k: clock[k] for k in CLOCK_KEYS} == A.public(ref["clock"], t_end, n), (precision, name, levels, call, clock, ref["clock"])
+            assert H.same(got, ref["state"]), (precision, name, levels, call)
+    _check_every_x(history)
+    _solo[key] = {"state": got, "clock": clock, "ref": dict(ref, history=history), "start": start}
+    return _solo[key]
+
+
+@pytest.mark.parametrize("n,family,levels,steps,exponents,floor_steps", FLOOR_CASES)
+@pytest.mark.parametrize("precision", [32, 64])
+def test_a_floor_that_binds_is_counted_once_the_step_is_taken_in_one_call_and_across_a_resumed_one(nbx, precision, n, family, levels, steps,
+                                                                                                  exponents, floor_steps):
+    st = R.make_state(precision, n, family)
+    whole = solo(nbx, precision, (n, family), st, levels, steps)
+    seam = solo(nbx, precision, (n, family), st, levels, steps, first=2)  # the floor_next the first call leaves is taken in the second
+    for d in (whole, seam):
+        assert [A.exponent(h) for _, h, _ in d["ref"]["history"]] == exponents and d["ref"]["clock"]["floor_steps"] == floor_steps, d["ref"]
+        assert d["clock"]["floor_steps"] == floor_steps and d["clock"]["steps"] == steps and not d["clock"]["done"]
+        assert d["clock"]["dt_next"] == 2.0 ** (K_CAP - levels)  # every case ends at its floor
+    assert H.same(whole["state"], seam["state"]) and whole["clock"] == seam["clock"]
+    print("fp%d n = %d %s levels %d: steps 2^%s, floor_steps %d" % (precision, n, family, levels, exponents, floor_steps))
+
+
+@pytest.mark.parametrize("precision", [32, 64])
+def test_one_floor_case_counts_some_of_its_steps_and_not_all(nbx, precision):
+    counts = [(solo(nbx, precision, (n, fam), R.make_state(precision, n, fam), levels, steps)["ref"]["clock"]["floor_steps"], steps)
+              for n, fam, levels, steps, _, _ in FLOOR_CASES]
+    assert any(0 < f < s for f, s in counts) and any(f == s for f, s in counts), counts
+
+
+@pytest.mark.parametrize("precision", [32, 64])
+def test_every_member_carries_its_own_floor_steps_and_keeps_them_once_it_is_done(nbx, precision):
+    """levels = 3, t_end = dt_cap, 12 steps asked: every member reaches t_end at the floor (2^-7) or, alone of its kind, at dt_cap
+    (n = 1); the launches of the steps that follow find it done and must leave its count alone while the others go on."""
+    def want(n, fam):
+        return solo(nbx, precision, (n, fam), R.make_state(precision, n, fam), FLOOR_LEVELS, FLOOR_MAX_STEPS, t_end=DT_CAP)
+
+    with nbx.Ensemble(5, len(FLOOR_ENSEMBLE), precision) as e:
+        e.upload([R.make_state(precision, n, fam) for n, fam in FLOOR_ENSEMBLE])
+        _adv(e, DT_CAP, FLOOR_MAX_STEPS, levels=FLOOR_LEVELS)
+        down, clocks = e.download(), e.clock()
+        for k, (n, fam) in enumerate(FLOOR_ENSEMBLE):
+            w = want(n, fam)
+            assert H.same({f: down[f][k] for f in H.POS + H.VEL}, w["state"]) and clocks[k] == w["clock"], (precision, k, clocks[k], w["clock"])
+    with nbx.Ragged([n for n, _ in FLOOR_RAGGED], precision) as r:
+        r.upload([R.make_state(precision, n, fam) for n, fam in FLOOR_RAGGED])
+        _adv(r, DT_CAP, 2, levels=FLOOR_LEVELS)
+        _adv(r, DT_CAP, FLOOR_MAX_STEPS - 2, resume=True, levels=FLOOR_LEVELS)
+        ragged = r.clock()
+        for k, ((n, fam), down) in enumerate(zip(FLOOR_RAGGED, r.download())):
+            w = want(n, fam)
+            assert H.same(down, w["state"]) and ragged[k] == w["clock"], (precision, k, ragged[k], w["clock"])
+    # on the restatement: all done, at different steps, with different counts; the first to finish has a count to keep
+    refs = [want(n, fam)["ref"]["clock"] for n, fam in FLOOR_ENSEMBLE + FLOOR_RAGGED[1:]]
+    assert all(c["t"] == DT_CAP and c["steps"] < FLOOR_MAX_STEPS for c in refs), refs
+    assert refs[0]["steps"] < refs[1]["steps"] and 0 < refs[0]["floor_steps"] < refs[1]["floor_steps"] and refs[0]["floor_next"], refs
+    assert (refs[-1]["steps"], refs[-1]["floor_steps"], refs[-1]["dt_last"]) == (1, 0, DT_CAP), refs[-1]  # n = 1
+    assert clocks[0]["floor_steps"] == refs[0]["floor_steps"] and ragged[2]["floor_steps"] == 0 and all(c["done"] for c in clocks + ragged)
+    print("fp%d: steps %s, floor_steps %s" % (precision, [c["steps"] for c in refs], [c["floor_steps"] for c in refs]))
+
+
+@pytest.mark.parametrize("n", COLD_SIZES)
+@pytest.mark.parametrize("precision", [32, 64])
+def test_a_system_at_rest_starts_at_dt_cap_and_shrinks_by_many_levels_at_once(nbx, precision, n):
+    """Six calls of one step from rest.  J is exactly 0 at the start, every start candidate +inf, so the first step is dt_cap
+    whatever it costs; the criterion then sees the jerk and drops the step by several levels in one go (jerk_ref.direct,
+    n = 257: 2^-4, 2^-10, 2^-16, 2^-17)."""
+    st = R.make_state(precision, n, "rest")
+    d = driven_from(nbx, precision, ("rest", n), st)
+    exps = [A.exponent(h) for h in d["steps"]]
+    assert np.isposinf(d["start"]).all() and len(d["start"]) == n and exps[0] == K_CAP, (exps, d["start"])
+    assert n == 5 or any(b < a - 1 for a, b in zip(exps, exps[1:])), exps  # five bodies are slow enough for one level at a time
+    assert min(exps) > K_CAP - LEVELS  # the floor does not hide it
+    for call, row in enumerate(d["rows"]):
+        assert {k: row["clock"][k] for k in CLOCK_KEYS} == row["ref"], (precision, n, call, row["clock"], row["ref"])
+        assert row["round_trip"] and row["fixed"] and row["moved"], (precision, n, call)
+    print("fp%d n = %d at rest: steps 2^%s, next 2^%d" % (precision, n, exps, A.exponent(d["clock"]["dt_next"])))
+
+
+def driven_from(nbx, precision, name, st):
+    """driven() for a state that is no family of a CASES entry, with the start candidates of the restatement."""
+    key = (precision,) + name
+    if key not in _driven:
+        n = len(st["mass"])
+        rows, ref = [], None
+        with nbx.Context(n, precision) as a, nbx.Context(n, precision) as b, nbx.Context(n, precision) as c:
+            ev = H.device_evaluate(b)
+            start = A.start_candidates(*ev(st))
+            _check_boundary(ETA * ETA * A.minimum(start))
+            a.upload(st)
+            c.upload(st)
+            for call in range(CALLS):
+                _adv(a, resume=call > 0)
+                ref = A.run(st if ref is None else ref["state"], precision, FAR, K_CAP, LEVELS, ETA, 1, ev, clock=ref and ref["clock"],
+                            carry=ref and ref["carry"])
+                (_, h, x), = ref["history"]
+                _check_boundary(x)
+                c.hermite_step(h, 1, resume=call > 0)
+                got = a.download()
+                rows.append({"clock": a.clock(), "ref": A.public(ref["clock"], FAR, n), "h": h, "round_trip": H.same(got, ref["state"]),
+                             "fixed": H.same(got, c.download()), "moved": not H.same(got, st)})
+        _driven[key] = {"rows": rows, "state": got, "clock": rows[-1]["clock"], "steps": [r["h"] for r in rows], "start": start}
+    return _driven[key]
+
+
+@pytest.mark.parametrize("precision", [32, 64])
+def test_members_at_rest_beside_a_moving_one_end_where_lone_contexts_end(nbx, precision):
+    states = [R.make_state(precision, n, fam) for n, fam in COLD_RAGGED]
+    with nbx.Ragged([n for n, _ in COLD_RAGGED], precision) as r:
+        r.upload(states)
+        _adv(r, max_steps=CALLS)
+        clocks = r.clock()
+        for k, ((n, fam), down) in enumerate(zip(COLD_RAGGED, r.download())):
+            w = solo(nbx, precision, (n, fam), states[k], LEVELS, CALLS)
+            assert H.same(down, w["state"]) and clocks[k] == w["clock"], (precision, k, clocks[k], w["clock"])
+            assert np.isposinf(w["start"]).all() == (fam == "rest")
+    assert clocks[0]["t"] != clocks[2]["t"] and clocks[1]["t"] != clocks[2]["t"]
+
+
+@pytest.mark.parametrize("name", ["massless", "coincident", "coincident massless"])
+@pytest.mark.parametrize("precision", [32, 64])
+def test_candidates_that_are_infinite_beside_finite_ones_leave_the_finite_ones_to_decide(nbx, precision, name):
+    """On the restatement: the massless cases hold +inf candidates next to a finite minimum, at the start and after every step
+    (a body that feels nothing has a zero denominator); the coincident pair with masses has none -- no pair of it is at rest
+    relative to a third body -- and every one of its values is finite, which is what the softening is for."""
+    st = degenerate_states(precision)[name]
+    n = len(st["mass"])
+    d = solo(nbx, precision, name, st, LEVELS, 3)
+    start = d["start"]
+    infinite = {"massless": [1], "coincident": [], "coincident massless": [0, 1]}[name]
+    assert np.flatnonzero(np.isposinf(start)).tolist() == infinite and not np.isnan(start).any(), start
+    assert math.isfinite(A.minimum(start)) and int(np.argmin(start)) not in infinite
+    assert all(math.isfinite(x) and x > 0.0 for _, _, x in d["ref"]["history"]), d["ref"]["history"]  # a finite minimum after every step
+    assert d["clock"]["steps"] == 3 and d["clock"]["floor_steps"] == 0 and 2.0 ** (K_CAP - LEVELS) < d["clock"]["dt_next"] <= DT_CAP
+    assert all(np.isfinite(d["state"][f]).all() for f in H.POS + H.VEL)
+    for i in infinite:  # the bodies that feel nothing keep their velocities: a1 = j1 = 0, so the denominator of the criterion is 0
+        assert all(d["state"][v][i] == st[v][i] for v in H.VEL), (name, i)
+    print("fp%d %s: start candidates %s, steps 2^%s" % (precision, name, start, [A.exponent(h) for _, h, _ in d["ref"]["history"]]))
+
+
+@pytest.mark.parametrize("precision", [32, 64])
+def test_a_member_whose_candidates_are_all_nan_or_infinite_steps_at_dt_cap_and_does_not_reach_the_member_before_it(nbx, precision):
+    """The construction of tests/test_jerk_gpu.py: (inf, nan, -inf) in one velocity of the second member.  Every jerk of that
+    member is a NaN, so every start candidate is +inf and every later one a NaN or +inf: q = +inf, never a NaN selected, three
+    steps of dt_cap and no floor step.  Its state is unspecified and not compared; member 0 is a lone context's, bit for bit."""
+    n = 513
+    st = R.make_state(precision, n, "cloud")
+    bad = {k: v.copy() for k, v in st.items()}
+    bad["vel_x"][0], bad["vel_y"][0], bad["vel_z"][0] = np.inf, np.nan, -np.inf
+    state, clock = lone(nbx, precision, n, "cloud", FAR, 3)
+    want = {"t": 3 * DT_CAP, "dt_last": DT_CAP, "dt_next": DT_CAP, "steps": 3, "floor_steps": 0}
+    with nbx.Ensemble(n, 2, precision) as e:
+        e.upload([st, bad])
+        _adv(e, max_steps=3)
+        down, clocks = e.download(), e.clock()
+        assert H.same({f: down[f][0] for f in H.POS + H.VEL}, state) and clocks[0] == clock, (precision, clocks[0], clock)
+        assert {k: clocks[1][k] for k in want} == want, clocks[1]
+    with nbx.Ragged([n, n], precision) as r:
+        r.upload([st, bad])
+        _adv(r, max_steps=3)
+        clocks = r.clock()
+        assert H.same(r.download()[0], state) and clocks[0] == clock, (precision, clocks[0], clock)
+        assert {k: clocks[1][k] for k in want} == want, clocks[1]
+    assert clock["dt_last"] < DT_CAP  # member 0's own steps are not the cap's: it did not take member 1's clock
 
 
 def test_an_adaptive_step_costs_at_most_twice_the_fixed_step_where_the_step_is_launch_bound(nbx):

@@ -9,7 +9,10 @@ holding its state ends.
 Shapes, the smallest at which each part can go wrong: n = 1, 2, 5; 257 (one column, two tiles with 255 padding records), 513 (a
 second column of one body), 2049 (five columns, two splits), 4097 (nine columns, four splits, the last one short), an ensemble of
 3 x 2049 and a ragged ensemble of (5, 2049, 257, 1, 513).  dt = 0.015 is no fp32 value (h is dt rounded to T) and is large enough
-for every rounding of the scheme to show in the bits of a few hundred bodies (tests/test_hermite_cpu.py says why)."""
+for every rounding of the scheme to show in the bits of a few hundred bodies (tests/test_hermite_cpu.py says why).
+
+The larger shapes -- 71 columns x 15 splits, 1038 columns of one split walking 2076 tiles, the largest member a batch object holds
+between small ones -- live in tests/test_large_steppers_gpu.py, held to the same round trip bit for bit."""
 import os
 import sys
 
