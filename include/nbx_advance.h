@@ -95,6 +95,10 @@
  * is neither 0 nor this library's; NBX_ERR_STATE where the object is not uploaded, has a local step pending or is a slice, or
  * where no advance call has been made on it; all before the first HIP call.
  *
+ * Unspecified results: a coordinate, a velocity component or a mass that is not finite, or whose square overflows T, gives
+ * unspecified values for every body and for the clock of that system, and of that system alone: the other systems' t, dt_last,
+ * dt_next, steps and floor_steps are what they are without it.
+ *
  * Deliberately not here: a step per body (block steps: this is the shared-step half of that); P(EC)^n; groups; a member range
  * (all members advance); tracers moving with the scheme; hipGraph replay; a command-line word or an environment knob in nbody.x.
  */

@@ -37,6 +37,9 @@
  *                  launches, kept for the object's life and freed by its destroy call
  * Every argument and state check comes before the first HIP call.
  *
+ * Unspecified results: a coordinate or a mass that is not finite, or a coordinate whose square overflows the object's precision,
+ * gives unspecified values for every body of that member, and of that member alone.
+ *
  * Deliberately not here: output to a device pointer (the arrays are host memory); accelerations in the reference summation
  * order or from the exact (validation) kernel -- members sum in the tree order of the one-launch kernel, as their steps do; a
  * potential per body; hipGraph replay.

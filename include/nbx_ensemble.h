@@ -20,6 +20,10 @@
  * kinetic energy is asked for): issuing a launch costs the host 3-4 us, and an ensemble worth creating has more pair work per
  * step than that.
  *
+ * Unspecified results: a coordinate, a velocity component or a mass that is not finite, or whose square overflows the
+ * ensemble's precision, gives unspecified values for every body of that member, and of that member alone: the other members'
+ * positions, velocities and kinetic energies are the bits they are without it.
+ *
  * Deliberately not here: members of different n (nbx_ragged.h has them); sharding one ensemble over GPUs (run one ensemble per GPU); nbx_accel for
  * ensembles (nbx_batch_accel.h has it); the reference summation order and the exact (validation) kernel; hipGraph replay; a command-line word in nbody.x
  * (its argv is the reference's).  The diagnostics of nbx_diag.h for the members of an ensemble are in nbx_ensemble_diag.h.

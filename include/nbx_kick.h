@@ -46,6 +46,10 @@
  *   NBX_ERR_STATE  a context has a local step awaiting nbx_commit
  * Every one of these checks comes before the first HIP call.
  *
+ * Unspecified results: a coordinate, a velocity component or a mass that is not finite, or whose square overflows the object's
+ * precision, gives unspecified values for every body of that system, and of that system alone: the other members of an
+ * ensemble or a ragged ensemble are kicked to the bits they are kicked to without it.
+ *
  * Deliberately not here: a kick size per member; a member range (all members are kicked, as a step call steps all of them); a
  * drift-only call; a command-line word or an environment knob in nbody.x (its output is the reference's); hipGraph replay of
  * kicks.

@@ -67,7 +67,10 @@
  * Every check but the last comes before the first HIP call.
  *
  * Unspecified results: a body with a coordinate that is not finite, or whose r2 overflows T for every partner, gives
- * unspecified values for that body only.
+ * unspecified values for that body, and that body is missing from the rows of the others: r2 to it is NaN or +infinity, which
+ * no strict compare against a row's +infinity passes.  Where k < n - 1 the other rows are then the rows of the system without
+ * it; where k >= n - 1 they end one entry early, index -1 and r2 +infinity where the body would have stood.  No other entry of
+ * another body's row changes, and other systems of the call are not touched.
  *
  * Cost: the pair loop compares every pair once and inserts rarely: for bodies in no particular order a body sees about
  * k ln(n / k) insertions.  Bodies sorted by decreasing distance from a body make that body insert at every pair: the result

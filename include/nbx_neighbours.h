@@ -67,7 +67,9 @@
  * Every check but the last comes before the first HIP call.
  *
  * Unspecified results: a body with a coordinate that is not finite, or whose r2 overflows T for every partner, gives
- * unspecified values for that body only.
+ * unspecified values for that body, and that body is nobody's nearest neighbour and within no finite radius of anybody: r2 to it is
+ * NaN or +infinity.  The other bodies' values are those of the system without it -- for n == 2, index -1, r2 +infinity and within 0.
+ * Other systems of the call are not touched.
  *
  * Deliberately not here: groups; device pointers for the results; k > 1 neighbours; a neighbour list (variable length);
  * relative velocities and bound or unbound tests (the arithmetic of nbx_timescale.h); merging bodies; hipGraph replay; a

@@ -22,6 +22,10 @@
  * Launches are plain launches on a non-blocking stream the ragged ensemble owns, one per step (plus one reduce launch where
  * the kinetic energy is asked for); no graph capture.
  *
+ * Unspecified results: a coordinate, a velocity component or a mass that is not finite, or whose square overflows the
+ * ensemble's precision, gives unspecified values for every body of that member, and of that member alone: the other members'
+ * positions, velocities and kinetic energies are the bits they are without it, whatever their sizes and places.
+ *
  * Deliberately not here: a time step per member; the diagnostics of nbx_diag.h for ragged members; sharding over GPUs (run
  * one ragged ensemble per GPU); nbx_accel (nbx_batch_accel.h has it); the reference summation order and the exact (validation) kernel; hipGraph replay;
  * a command-line word in nbody.x (its argv is the reference's).  Velocity-only half steps, which make the steps of every member

@@ -14,6 +14,9 @@
  * (owning all of them, same precision) that holds the member's state -- the same kernel body over the same workgroups, the same
  * partial rows, the same reduce order.  Members do not see each other; the result does not depend on first, on count, on the
  * member's place in the ragged ensemble or on its neighbours' sizes.
+ *
+ * Unspecified results: a coordinate, a velocity component or a mass that is not finite, or whose square overflows the
+ * ensemble's precision, gives unspecified values for the entry of that member, and of that member alone.
  */
 #ifndef NBX_RAGGED_DIAG_H
 #define NBX_RAGGED_DIAG_H

@@ -54,6 +54,9 @@
  *   NBX_ERR_ALLOC  the partials did not fit
  * Every check but the last comes before the first HIP call.  count == 0 returns NBX_OK and writes nothing.
  *
+ * Unspecified results: a coordinate, a velocity component or a mass that is not finite, or whose square overflows T, gives
+ * unspecified values for the entry of that system, and of that system alone.
+ *
  * Deliberately not here: groups and sliced contexts; the indices of the extreme pair; a value per body; a dt per member (dt
  * stays one value per step call, this call only helps choose it); a command-line word or an environment knob in nbody.x (its
  * output is the reference's); hipGraph replay.
