@@ -29,31 +29,31 @@ $(PKG)/nbx_kick.o: $(CSRC)/nbx_kick.hip $(CSRC)/nbx_kick_kernels.hpp $(CSRC)/nbx
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(PKG)/nbx_timescale.o: $(CSRC)/nbx_timescale.hip $(CSRC)/nbx_timescale_kernels.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_timescale.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_field.o: $(CSRC)/nbx_field.hip $(CSRC)/nbx_field_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_field.h
+$(PKG)/nbx_field.o: $(CSRC)/nbx_field.hip $(CSRC)/nbx_field_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_tilewalk.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_field.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_neighbours.o: $(CSRC)/nbx_neighbours.hip $(CSRC)/nbx_neighbours_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_neighbours.h
+$(PKG)/nbx_neighbours.o: $(CSRC)/nbx_neighbours.hip $(CSRC)/nbx_neighbours_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_tilewalk.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_neighbours.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_paircount.o: $(CSRC)/nbx_paircount.hip $(CSRC)/nbx_paircount_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_paircount.h
+$(PKG)/nbx_paircount.o: $(CSRC)/nbx_paircount.hip $(CSRC)/nbx_paircount_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_tilewalk.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_paircount.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_tracers.o: $(CSRC)/nbx_tracers.hip $(CSRC)/nbx_tracers_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_tracers.h
+$(PKG)/nbx_tracers.o: $(CSRC)/nbx_tracers.hip $(CSRC)/nbx_tracers_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_tilewalk.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_tracers.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_knn.o: $(CSRC)/nbx_knn.hip $(CSRC)/nbx_knn_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_knn.h
+$(PKG)/nbx_knn.o: $(CSRC)/nbx_knn.hip $(CSRC)/nbx_knn_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_tilewalk.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_knn.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_fof.o: $(CSRC)/nbx_fof.hip $(CSRC)/nbx_fof_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_fof.h
+$(PKG)/nbx_fof.o: $(CSRC)/nbx_fof.hip $(CSRC)/nbx_fof_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_tilewalk.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_fof.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_binaries.o: $(CSRC)/nbx_binaries.hip $(CSRC)/nbx_binaries_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_binaries.h
+$(PKG)/nbx_binaries.o: $(CSRC)/nbx_binaries.hip $(CSRC)/nbx_binaries_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_tilewalk.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_binaries.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_tidal.o: $(CSRC)/nbx_tidal.hip $(CSRC)/nbx_tidal_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_tidal.h
+$(PKG)/nbx_tidal.o: $(CSRC)/nbx_tidal.hip $(CSRC)/nbx_tidal_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_tilewalk.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_tidal.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_clumps.o: $(CSRC)/nbx_clumps.hip $(CSRC)/nbx_clumps_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_clumps.h
+$(PKG)/nbx_clumps.o: $(CSRC)/nbx_clumps.hip $(CSRC)/nbx_clumps_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_tilewalk.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_clumps.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_nlist.o: $(CSRC)/nbx_nlist.hip $(CSRC)/nbx_nlist_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_nlist_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_nlist.h
+$(PKG)/nbx_nlist.o: $(CSRC)/nbx_nlist.hip $(CSRC)/nbx_nlist_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_tilewalk.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_nlist_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_nlist.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_jerk.o: $(CSRC)/nbx_jerk.hip $(CSRC)/nbx_jerk_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_jerk.h
+$(PKG)/nbx_jerk.o: $(CSRC)/nbx_jerk.hip $(CSRC)/nbx_jerk_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_tilewalk.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_jerk.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_hermite.o: $(CSRC)/nbx_hermite.hip $(CSRC)/nbx_hermite_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_hermite.h
+$(PKG)/nbx_hermite.o: $(CSRC)/nbx_hermite.hip $(CSRC)/nbx_hermite_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_tilewalk.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_hermite.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(PKG)/nbx_advance.o: $(CSRC)/nbx_advance.hip $(CSRC)/nbx_advance_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_advance.h
+$(PKG)/nbx_advance.o: $(CSRC)/nbx_advance.hip $(CSRC)/nbx_advance_kernels.hpp $(CSRC)/nbx_analysis.hpp $(CSRC)/nbx_tilewalk.hpp $(CSRC)/nbx_field_shape.hpp $(CSRC)/nbx_ensemble_internal.hpp $(CSRC)/nbx_ragged_internal.hpp $(CSRC)/nbx_batch.hpp $(CSRC)/nbx_internal.hpp $(CSRC)/nbx_object.hpp $(CSRC)/nbx_plan.hpp $(CSRC)/nbx_diag_shape.hpp $(CSRC)/nbx_pair.hpp include/nbx.h include/nbx_diag.h include/nbx_ensemble.h include/nbx_ragged.h include/nbx_advance.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(PKG)/nbx_ic.o: $(CSRC)/nbx_ic.cpp include/nbx.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -Wall -ffp-contract=off -c $< -o $@

@@ -200,7 +200,7 @@ int advance_t(nbx_ragged* r, const char* where, const AdvancePlan& p) {
   using T4 = typename V4<T>::type;
   // the copy's source, herm_tab_src, lives with the object: nothing here waits for it
   const int rc = ragged_member_table<AdvanceMember>(r, &r->herm_tab, &r->herm_tab_src, where, [](const MemberSpan& mem, unsigned long long out_off) {
-    return AdvanceMember{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, out_off, mem.n, 0};
+    return AdvanceMember{{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, out_off, mem.n, 0}};
   });
   if (rc) return rc;
   const GridExtents g = ragged_extents(r, 0, r->members);

@@ -56,6 +56,7 @@
 
 #include "nbx_field_shape.hpp"
 #include "nbx_pair.hpp"
+#include "nbx_tilewalk.hpp"
 
 namespace nbx {
 
@@ -164,14 +165,6 @@ __device__ __forceinline__ void advance_pair2(const float4 r, const float4 w, f3
   q.jz = __builtin_elementwise_fma(tz, s, q.jz);
 }
 
-// A velocity tile record, read whole: the pair needs three components, and left to itself the compiler narrows the fp32 read to
-// 12 bytes (ds_read_b96), which occupies the LDS twice as long as the 16-byte read; the empty statement keeps .w alive.
-__device__ __forceinline__ float4 advance_velocity(const float4* tile, const int j) {
-  const float4 r = tile[j];
-  asm volatile("" ::"v"(r.w));
-  return r;
-}
-
 // What a lane keeps for its two bodies: fp32 packs them, body 0 in .x and body 1 in .y of every value; fp64 holds two scalars.
 // No arrays: every value has a name, so every value has a register.
 template <typename T> struct AdvanceLane;
@@ -192,7 +185,7 @@ template <> struct AdvanceLane<float> {
   }
   __device__ __forceinline__ void tile(const float4* ptile, const float4* vtile) {
 #pragma unroll 4
-    for (int j = 0; j < kTile; ++j) advance_pair2(ptile[j], advance_velocity(vtile, j), x, y, z, u, v, w, q);
+    for (int j = 0; j < kTile; ++j) advance_pair2(ptile[j], whole_record(vtile, j), x, y, z, u, v, w, q);
   }
 };
 template <> struct AdvanceLane<double> {
@@ -341,14 +334,8 @@ __global__ __launch_bounds__(kBlock) void ensemble_advance_kernel(const Ensemble
                   a.parts + 2 * k * gridDim.y * (size_t)a.n, blockIdx.x, blockIdx.y, a.predict, hc);
 }
 
-// one entry per member of a ragged ensemble: the fixed stepper's table (the same layout: whichever call comes first builds it)
-struct AdvanceMember {
-  unsigned long long pos_off;  // the member's first record in posm
-  unsigned long long vel_off;  // the member's first record in velm
-  unsigned long long out_off;  // the bodies of the members before it
-  int n;
-  int reserved;
-};
+// the fixed stepper's table (the same layout: whichever call comes first builds it)
+struct AdvanceMember : VelMember {};
 
 template <typename T>
 struct RaggedAdvanceArgs {
@@ -363,9 +350,10 @@ struct RaggedAdvanceArgs {
 
 template <typename T>
 __global__ __launch_bounds__(kBlock) void ragged_advance_kernel(const RaggedAdvanceArgs<T> r) {
-  const AdvanceMember mem = r.table[blockIdx.z];
-  const FieldShape s = field_shape(mem.n, mem.n);
-  if ((int)blockIdx.x >= s.columns || (int)blockIdx.y >= s.splits) return;  // the whole workgroup: another, larger member's
+  const MemberGroup<AdvanceMember> g = member_group(r.table, 0u);
+  if (g.elsewhere()) return;
+  const AdvanceMember& mem = g.mem;
+  const FieldShape& s = g.shape;
   bool done;
   const AdvanceConsts hc = advance_consts(r.tm, blockIdx.z, &done);
   if (r.predict && done) return;

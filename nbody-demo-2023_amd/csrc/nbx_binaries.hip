@@ -105,7 +105,7 @@ int binaries_members_t(nbx_ragged* r, const char* where, int first, int count, c
   using T4 = typename V4<T>::type;
   std::vector<BoundMember> table;  // lives until run_binaries has synchronised
   const int rc = ragged_member_table<BoundMember>(r, &r->bin_tab, &table, where, [](const MemberSpan& mem, unsigned long long out_off) {
-    return BoundMember{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, out_off, mem.n, 0};
+    return BoundMember{{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, out_off, mem.n, 0}};
   });
   if (rc) return rc;
   const GridExtents g = ragged_extents(r, first, count);

@@ -47,6 +47,7 @@
 
 #include "nbx_field_shape.hpp"
 #include "nbx_pair.hpp"
+#include "nbx_tilewalk.hpp"
 
 namespace nbx {
 
@@ -100,15 +101,6 @@ __device__ __forceinline__ void bound_take(const T e, const int jg, const int n,
   if constexpr (COUNT) cnt += neg ? 1 : 0;
 }
 
-// A velocity tile record, read whole.  The pair needs its three components alone, and left to itself the compiler narrows the
-// fp32 read to 12 bytes (ds_read_b96), which occupies the LDS twice as long as the 16-byte read (ds_read_b128): the empty
-// statement keeps .w alive and costs no instruction.
-__device__ __forceinline__ float4 bound_velocity(const float4* tile, const int j) {
-  const float4 r = tile[j];
-  asm volatile("" ::"v"(r.w));
-  return r;
-}
-
 // One LDS tile against the lane's B bodies (j_glob: global index of tile record 0).
 template <typename T, int B, bool MASK, bool COUNT>
 __device__ __forceinline__ void bound_tile(const typename V4<T>::type* ptile, const typename V4<T>::type* vtile, const int j_glob,
@@ -131,7 +123,7 @@ __device__ __forceinline__ void bound_tile(const typename V4<T>::type* ptile, co
 #pragma unroll 4
     for (int j = 0; j < kTile; ++j) {
       const float4 r = ptile[j];
-      const float4 s = bound_velocity(vtile, j);
+      const float4 s = whole_record(vtile, j);
       const int jg = j_glob + j;
 #pragma unroll
       for (int h = 0; h < B / 2; ++h) {
@@ -179,8 +171,7 @@ __device__ __forceinline__ void bound_body(const typename V4<T>::type* __restric
   __shared__ T4 vtile[kTile];
   const int t = threadIdx.x;
   const int l0 = col * (kBlock * B);  // first body of this workgroup
-  T4 zero;
-  zero.x = zero.y = zero.z = zero.w = (T)0;
+  const T4 zero = zero_record<T4>();
   T xi[B], yi[B], zi[B], gi[B], ui[B], vi[B], wi[B], best[B];
   int ig[B], bj[B], cnt[B];
 #pragma unroll
@@ -221,7 +212,7 @@ __device__ __forceinline__ void bound_body(const typename V4<T>::type* __restric
       if (j < n) next_v = velm[j];
     }
     const int j0 = k * kTile;
-    if ((j0 < g_hi && j0 + kTile > g_lo) || j0 + kTile > n)
+    if (tile_masked(j0, g_lo, g_hi, n))
       bound_tile<T, B, true, COUNT>(ptile, vtile, j0, n, xi, yi, zi, gi, ui, vi, wi, ig, best, bj, cnt);
     else
       bound_tile<T, B, false, COUNT>(ptile, vtile, j0, n, xi, yi, zi, gi, ui, vi, wi, ig, best, bj, cnt);
@@ -264,14 +255,7 @@ __global__ __launch_bounds__(kBlock) void ensemble_bound_kernel(const EnsembleBo
                                      e.parts + k * gridDim.y * (size_t)e.n, blockIdx.x, blockIdx.y);
 }
 
-// one entry per member of a ragged ensemble, built on first use and fixed for the object's life
-struct BoundMember {
-  unsigned long long pos_off;  // the member's first record in posm
-  unsigned long long vel_off;  // the member's first record in velm
-  unsigned long long out_off;  // the bodies of the members before it: where its results begin in a call that starts at member 0
-  int n;
-  int reserved;
-};
+struct BoundMember : VelMember {};
 
 template <typename T>
 struct RaggedBoundArgs {
@@ -284,39 +268,24 @@ struct RaggedBoundArgs {
 
 template <typename T, bool COUNT>
 __global__ __launch_bounds__(kBlock) void ragged_bound_kernel(const RaggedBoundArgs<T> r) {
-  const BoundMember mem = r.table[r.first + blockIdx.z];
-  const FieldShape s = field_shape(mem.n, mem.n);
-  if ((int)blockIdx.x >= s.columns || (int)blockIdx.y >= s.splits) return;  // the whole workgroup: another, larger member's
-  const size_t rel = (size_t)(mem.out_off - r.table[r.first].out_off);     // the bodies of the range before this member
-  bound_body<T, kBoundBodies, COUNT>(r.posm + mem.pos_off, r.velm + mem.vel_off, mem.n, s.tiles_per_split, r.parts + rel * gridDim.y,
-                                     blockIdx.x, blockIdx.y);
+  const MemberGroup<BoundMember> g = member_group(r.table, r.first);
+  if (g.elsewhere()) return;
+  bound_body<T, kBoundBodies, COUNT>(r.posm + g.mem.pos_off, r.velm + g.mem.vel_off, g.mem.n, g.shape.tiles_per_split,
+                                     r.parts + g.rel() * gridDim.y, blockIdx.x, blockIdx.y);
 }
 
-// Body idx of the call's `total` bodies.  table == nullptr: every system has n_all bodies, member idx / n_all of the range.
-// Otherwise the member is the last of table[first .. first + count) whose out_off, taken from member first, is not above idx.
-// The member has field_shape(n, n).splits rows of n records; its rows begin at (the bodies of the range before it) * row_splits,
-// row_splits the gridDim.y of the pair-work launch.  The winner's doubled energy is halved: exact, +inf stays +inf.
+// Body idx of the call's `total` bodies, its member found by member_at..  The member has field_shape(n, n).splits rows of n
+// records; its rows begin at (the bodies of the range before it) * row_splits, row_splits the gridDim.y of the pair-work
+// launch..  The winner's doubled energy is halved: exact, +inf stays +inf.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void bound_finish_kernel(const BoundRecord<T>* __restrict__ parts, const BoundMember* __restrict__ table,
                                                               unsigned first, int count, int n_all, int row_splits, unsigned total,
                                                               BoundRecord<T>* __restrict__ out) {
   const unsigned idx = blockIdx.x * (unsigned)kBlock + threadIdx.x;
   if (idx >= total) return;
-  int n = n_all;
-  size_t rel = 0;  // the bodies of the range before the body's member
-  if (table) {
-    const unsigned long long base = table[first].out_off;
-    int lo = 0, hi = count - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (table[first + mid].out_off - base <= idx) lo = mid;
-      else hi = mid - 1;
-    }
-    n = table[first + lo].n;
-    rel = (size_t)(table[first + lo].out_off - base);
-  } else {
-    rel = (size_t)(idx / (unsigned)n_all) * (size_t)n_all;
-  }
+  const MemberAt at = member_at(table, first, count, n_all, idx);
+  const int n = at.n;
+  const size_t rel = at.rel;  // the bodies of the range before the body's member
   const int splits = field_shape(n, n).splits;
   const BoundRecord<T>* row = parts + rel * (size_t)row_splits + ((size_t)idx - rel);
   BoundRecord<T> o;

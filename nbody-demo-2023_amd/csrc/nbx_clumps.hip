@@ -160,7 +160,7 @@ int clumps_members_t(nbx_ragged* r, const char* where, int first, int count, con
     ~Drain() { if (armed) (void)hipStreamSynchronize(stream); }
   } drain{r->stream, false};
   rc = ragged_member_table<ClumpMember>(r, &r->clump_tab, &table, where, [](const MemberSpan& mem, unsigned long long out_off) {
-    return ClumpMember{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, out_off, mem.n, 0};
+    return ClumpMember{{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, out_off, mem.n, 0}};
   });
   if (rc) return rc;  // nothing was enqueued
   drain.armed = !table.empty();  // this call has built the table: its copy is in flight

@@ -44,6 +44,7 @@
 
 #include "nbx_field_shape.hpp"
 #include "nbx_pair.hpp"
+#include "nbx_tilewalk.hpp"
 
 namespace nbx {
 
@@ -203,8 +204,7 @@ __device__ __forceinline__ void clump_body(const typename V4<T>::type* __restric
   __shared__ T4 vtile[kTile];
   const int t = threadIdx.x;
   const int l0 = col * (kBlock * B);  // first body of this workgroup
-  T4 zero;
-  zero.x = zero.y = zero.z = zero.w = (T)0;
+  const T4 zero = zero_record<T4>();
   ClumpLane<T> lane;
 #pragma unroll
   for (int b = 0; b < B; ++b) {
@@ -301,14 +301,7 @@ __global__ __launch_bounds__(kBlock) void ensemble_clump_kernel(const EnsembleCl
                 e.tiles_per_split, e.parts + 2 * rows, e.counts + rows, blockIdx.x, blockIdx.y);
 }
 
-// one entry per member of a ragged ensemble, built on first use and fixed for the object's life
-struct ClumpMember {
-  unsigned long long pos_off;  // the member's first record in posm
-  unsigned long long vel_off;  // the member's first record in velm
-  unsigned long long out_off;  // the bodies of the members before it: where its labels and results begin in a call from member 0
-  int n;
-  int reserved;
-};
+struct ClumpMember : VelMember {};
 
 template <typename T>
 struct RaggedClumpArgs {
@@ -323,13 +316,11 @@ struct RaggedClumpArgs {
 
 template <typename T>
 __global__ __launch_bounds__(kBlock) void ragged_clump_kernel(const RaggedClumpArgs<T> r) {
-  const ClumpMember mem = r.table[r.first + blockIdx.z];
-  const FieldShape s = field_shape(mem.n, mem.n);
-  if ((int)blockIdx.x >= s.columns || (int)blockIdx.y >= s.splits) return;  // the whole workgroup: another, larger member's
-  const size_t rel = (size_t)(mem.out_off - r.table[r.first].out_off);     // the bodies of the range before this member
-  const size_t rows = rel * gridDim.y;
-  clump_body<T>(r.posm + mem.pos_off, r.velm + mem.vel_off, r.lab + rel, mem.n, s.tiles_per_split, r.parts + 2 * rows, r.counts + rows,
-                blockIdx.x, blockIdx.y);
+  const MemberGroup<ClumpMember> g = member_group(r.table, r.first);
+  if (g.elsewhere()) return;
+  const size_t rel = g.rel(), rows = rel * gridDim.y;
+  clump_body<T>(r.posm + g.mem.pos_off, r.velm + g.mem.vel_off, r.lab + rel, g.mem.n, g.shape.tiles_per_split, r.parts + 2 * rows,
+                r.counts + rows, blockIdx.x, blockIdx.y);
 }
 
 // what the finish kernel reads besides the partials: where a body's own records are

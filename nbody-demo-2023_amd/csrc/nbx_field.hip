@@ -107,7 +107,7 @@ int field_members_t(nbx_ragged* r, const char* where, int first, int count, int 
   using T4 = typename V4<T>::type;
   std::vector<FieldMember> table;  // lives until run_field has synchronised
   const int rc = ragged_member_table<FieldMember>(r, &r->field_tab, &table, where, [](const MemberSpan& mem, unsigned long long) {
-    return FieldMember{(unsigned long long)mem.pos_off, mem.n, 0};
+    return FieldMember{{(unsigned long long)mem.pos_off, mem.n, 0}};
   });
   if (rc) return rc;
   const GridExtents g = ragged_extents(r, first, count, m);  // m > 0: every member has the same columns

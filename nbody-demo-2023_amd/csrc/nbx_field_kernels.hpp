@@ -38,6 +38,7 @@
 
 #include "nbx_field_shape.hpp"
 #include "nbx_pair.hpp"
+#include "nbx_tilewalk.hpp"
 
 namespace nbx {
 
@@ -104,8 +105,7 @@ __device__ __forceinline__ void field_body(const typename V4<T>::type* __restric
   __shared__ T4 tile[kTile];
   const int t = threadIdx.x;
   const int l0 = col * (kBlock * B);  // first point of this workgroup
-  T4 zero;
-  zero.x = zero.y = zero.z = zero.w = (T)0;
+  const T4 zero = zero_record<T4>();
   T xi[B], yi[B], zi[B], ax[B], ay[B], az[B], ph[B];
 #pragma unroll
   for (int b = 0; b < B; ++b) {
@@ -115,15 +115,9 @@ __device__ __forceinline__ void field_body(const typename V4<T>::type* __restric
     xi[b] = p.x; yi[b] = p.y; zi[b] = p.z;
     ax[b] = ay[b] = az[b] = ph[b] = (T)0;
   }
-  const int tiles = (n + kTile - 1) / kTile;
-  const int k0 = split * tiles_per_split, k1 = min(tiles, k0 + tiles_per_split);
-  T4 next = zero;
-  if (k0 < k1) next = posm[k0 * kTile + t];
-  for (int k = k0; k < k1; ++k) {
-    __syncthreads();  // every lane is done with the previous tile
-    tile[t] = next;
-    __syncthreads();
-    if (k + 1 < k1) next = posm[(k + 1) * kTile + t];
+  TileWalk<T4> walk(posm, n, split, tiles_per_split);
+  for (int k = walk.k0; k < walk.k1; ++k) {
+    walk.stage(tile, k);
     if constexpr (sizeof(T) == 4 && B % 2 == 0) {
       f32x2 px[B / 2], py[B / 2], pz[B / 2], qx[B / 2], qy[B / 2], qz[B / 2], qp[B / 2];
 #pragma unroll
@@ -194,12 +188,7 @@ __global__ __launch_bounds__(kBlock) void ensemble_field_kernel(const EnsembleFi
                                  e.parts + k * gridDim.y * (size_t)e.m, blockIdx.x, blockIdx.y);
 }
 
-// one entry per member of a ragged ensemble, built on first use and fixed for the object's life
-struct FieldMember {
-  unsigned long long pos_off;  // the member's first record in posm
-  int n;
-  int reserved;
-};
+struct FieldMember : PosMember {};
 
 template <typename T>
 struct RaggedFieldArgs {
@@ -214,10 +203,9 @@ struct RaggedFieldArgs {
 template <typename T>
 __global__ __launch_bounds__(kBlock) void ragged_field_kernel(const RaggedFieldArgs<T> r) {
   const size_t k = blockIdx.z;
-  const FieldMember mem = r.table[r.first + k];
-  const FieldShape s = field_shape(r.m, mem.n);
-  if ((int)blockIdx.y >= s.splits) return;  // the whole workgroup: this split is another, larger member's
-  field_body<T, kFieldPoints<T>>(r.posm + mem.pos_off, mem.n, r.pts + k * (size_t)r.m, r.m, s.tiles_per_split,
+  const MemberGroup<FieldMember> g = member_group(r.table, r.first, r.m);
+  if ((int)blockIdx.y >= g.shape.splits) return;  // the whole workgroup: this split is another, larger member's
+  field_body<T, kFieldPoints<T>>(r.posm + g.mem.pos_off, g.mem.n, r.pts + k * (size_t)r.m, r.m, g.shape.tiles_per_split,
                                  r.parts + k * gridDim.y * (size_t)r.m, blockIdx.x, blockIdx.y);
 }
 

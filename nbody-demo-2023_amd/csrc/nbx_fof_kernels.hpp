@@ -39,6 +39,7 @@
 
 #include "nbx_field_shape.hpp"
 #include "nbx_pair.hpp"
+#include "nbx_tilewalk.hpp"
 
 namespace nbx {
 
@@ -137,16 +138,9 @@ __device__ __forceinline__ void fof_body(const typename V4<T>::type* __restrict_
     xi[b] = p.x; yi[b] = p.y; zi[b] = p.z;
     best[b] = kFofNone;
   }
-  const int tiles = (n + kTile - 1) / kTile;
-  const int k0 = split * tiles_per_split, k1 = min(tiles, k0 + tiles_per_split);
-  T4 next;
-  next.x = next.y = next.z = next.w = (T)0;
-  if (k0 < k1) next = rec[k0 * kTile + t];
-  for (int k = k0; k < k1; ++k) {
-    __syncthreads();  // every lane is done with the previous tile
-    tile[t] = next;
-    __syncthreads();
-    if (k + 1 < k1) next = rec[(k + 1) * kTile + t];
+  TileWalk<T4> walk(rec, n, split, tiles_per_split);
+  for (int k = walk.k0; k < walk.k1; ++k) {
+    walk.stage(tile, k);
     fof_tile<T, B>(tile, xi, yi, zi, h2, best);
   }
 #pragma unroll

@@ -45,6 +45,7 @@
 
 #include "nbx_field_shape.hpp"
 #include "nbx_pair.hpp"
+#include "nbx_tilewalk.hpp"
 
 namespace nbx {
 
@@ -136,14 +137,6 @@ __device__ __forceinline__ void hermite_pair2(const float4 r, const float4 w, f3
   q.jz = __builtin_elementwise_fma(tz, s, q.jz);
 }
 
-// A velocity tile record, read whole: the pair needs three components, and left to itself the compiler narrows the fp32 read to
-// 12 bytes (ds_read_b96), which occupies the LDS twice as long as the 16-byte read; the empty statement keeps .w alive.
-__device__ __forceinline__ float4 hermite_velocity(const float4* tile, const int j) {
-  const float4 r = tile[j];
-  asm volatile("" ::"v"(r.w));
-  return r;
-}
-
 // What a lane keeps for its two bodies: fp32 packs them, body 0 in .x and body 1 in .y of every value; fp64 holds two scalars.
 // No arrays: every value has a name, so every value has a register.
 template <typename T> struct HermiteLane;
@@ -164,7 +157,7 @@ template <> struct HermiteLane<float> {
   }
   __device__ __forceinline__ void tile(const float4* ptile, const float4* vtile) {
 #pragma unroll 4
-    for (int j = 0; j < kTile; ++j) hermite_pair2(ptile[j], hermite_velocity(vtile, j), x, y, z, u, v, w, q);
+    for (int j = 0; j < kTile; ++j) hermite_pair2(ptile[j], whole_record(vtile, j), x, y, z, u, v, w, q);
   }
 };
 template <> struct HermiteLane<double> {
@@ -300,14 +293,7 @@ __global__ __launch_bounds__(kBlock) void ensemble_hermite_kernel(const Ensemble
                   a.parts + 2 * k * gridDim.y * (size_t)a.n, blockIdx.x, blockIdx.y, a.predict, a.hc);
 }
 
-// one entry per member of a ragged ensemble, built on first use and fixed for the object's life
-struct HermiteMember {
-  unsigned long long pos_off;  // the member's first record in posm
-  unsigned long long vel_off;  // the member's first record in velm
-  unsigned long long out_off;  // the bodies of the members before it
-  int n;
-  int reserved;
-};
+struct HermiteMember : VelMember {};
 
 template <typename T>
 struct RaggedHermiteArgs {
@@ -322,9 +308,10 @@ struct RaggedHermiteArgs {
 
 template <typename T>
 __global__ __launch_bounds__(kBlock) void ragged_hermite_kernel(const RaggedHermiteArgs<T> r) {
-  const HermiteMember mem = r.table[blockIdx.z];
-  const FieldShape s = field_shape(mem.n, mem.n);
-  if ((int)blockIdx.x >= s.columns || (int)blockIdx.y >= s.splits) return;  // the whole workgroup: another, larger member's
+  const MemberGroup<HermiteMember> g = member_group(r.table, 0u);
+  if (g.elsewhere()) return;
+  const HermiteMember& mem = g.mem;
+  const FieldShape& s = g.shape;
   hermite_body<T>(r.posm + mem.pos_off, r.velm + mem.vel_off, r.keep + 2 * mem.vel_off, mem.n, s.tiles_per_split,
                   r.parts + 2 * (size_t)mem.out_off * gridDim.y, blockIdx.x, blockIdx.y, r.predict, r.hc);
 }

@@ -100,7 +100,7 @@ int jerk_members_t(nbx_ragged* r, const char* where, int first, int count, const
   using T4 = typename V4<T>::type;
   std::vector<JerkMember> table;  // lives until run_jerk has synchronised
   const int rc = ragged_member_table<JerkMember>(r, &r->jerk_tab, &table, where, [](const MemberSpan& mem, unsigned long long out_off) {
-    return JerkMember{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, out_off, mem.n, 0};
+    return JerkMember{{(unsigned long long)mem.pos_off, (unsigned long long)mem.vel_off, out_off, mem.n, 0}};
   });
   if (rc) return rc;
   const GridExtents g = ragged_extents(r, first, count);

@@ -44,6 +44,7 @@
 
 #include "nbx_field_shape.hpp"
 #include "nbx_pair.hpp"
+#include "nbx_tilewalk.hpp"
 
 namespace nbx {
 
@@ -109,15 +110,6 @@ __device__ __forceinline__ void jerk_pair2(const float4 r, const float4 w, f32x2
   q.jz = __builtin_elementwise_fma(tz, s, q.jz);
 }
 
-// A velocity tile record, read whole.  The pair needs its three components alone, and left to itself the compiler narrows the
-// fp32 read to 12 bytes (ds_read_b96), which occupies the LDS twice as long as the 16-byte read (ds_read_b128): the empty
-// statement keeps .w alive and costs no instruction.
-__device__ __forceinline__ float4 jerk_velocity(const float4* tile, const int j) {
-  const float4 r = tile[j];
-  asm volatile("" ::"v"(r.w));
-  return r;
-}
-
 // What a lane keeps for its two bodies: fp32 packs them, body 0 in .x and body 1 in .y of every value; fp64 holds two scalars.
 // No arrays: every value has a name, so every value has a register.
 template <typename T> struct JerkLane;
@@ -138,7 +130,7 @@ template <> struct JerkLane<float> {
   }
   __device__ __forceinline__ void tile(const float4* ptile, const float4* vtile) {
 #pragma unroll 4
-    for (int j = 0; j < kTile; ++j) jerk_pair2(ptile[j], jerk_velocity(vtile, j), x, y, z, u, v, w, q);
+    for (int j = 0; j < kTile; ++j) jerk_pair2(ptile[j], whole_record(vtile, j), x, y, z, u, v, w, q);
   }
 };
 template <> struct JerkLane<double> {
@@ -177,8 +169,7 @@ __device__ __forceinline__ void jerk_body(const typename V4<T>::type* __restrict
   __shared__ T4 vtile[kTile];
   const int t = threadIdx.x;
   const int l0 = col * (kBlock * B);  // first body of this workgroup
-  T4 zero;
-  zero.x = zero.y = zero.z = zero.w = (T)0;
+  const T4 zero = zero_record<T4>();
   JerkLane<T> lane;
 #pragma unroll
   for (int b = 0; b < B; ++b) {
@@ -191,25 +182,9 @@ __device__ __forceinline__ void jerk_body(const typename V4<T>::type* __restrict
     lane.load(b, p, v);
   }
   lane.clear();
-  const int tiles = (n + kTile - 1) / kTile;
-  const int k0 = split * tiles_per_split, k1 = min(tiles, k0 + tiles_per_split);
-  T4 next_p = zero, next_v = zero;
-  if (k0 < k1) {
-    const int j = k0 * kTile + t;
-    next_p = posm[j];
-    if (j < n) next_v = velm[j];
-  }
-  for (int k = k0; k < k1; ++k) {
-    __syncthreads();  // every lane is done with the previous tile
-    ptile[t] = next_p;
-    vtile[t] = next_v;
-    __syncthreads();
-    if (k + 1 < k1) {
-      const int j = (k + 1) * kTile + t;
-      next_p = posm[j];
-      next_v = zero;
-      if (j < n) next_v = velm[j];
-    }
+  TileWalk2<T4> walk(posm, velm, n, split, tiles_per_split);
+  for (int k = walk.k0; k < walk.k1; ++k) {
+    walk.stage(ptile, vtile, k);
     lane.tile(ptile, vtile);
   }
 #pragma unroll
@@ -254,14 +229,7 @@ __global__ __launch_bounds__(kBlock) void ensemble_jerk_kernel(const EnsembleJer
                e.parts + 2 * k * gridDim.y * (size_t)e.n, blockIdx.x, blockIdx.y);
 }
 
-// one entry per member of a ragged ensemble, built on first use and fixed for the object's life
-struct JerkMember {
-  unsigned long long pos_off;  // the member's first record in posm
-  unsigned long long vel_off;  // the member's first record in velm
-  unsigned long long out_off;  // the bodies of the members before it: where its results begin in a call that starts at member 0
-  int n;
-  int reserved;
-};
+struct JerkMember : VelMember {};
 
 template <typename T>
 struct RaggedJerkArgs {
@@ -274,17 +242,15 @@ struct RaggedJerkArgs {
 
 template <typename T>
 __global__ __launch_bounds__(kBlock) void ragged_jerk_kernel(const RaggedJerkArgs<T> r) {
-  const JerkMember mem = r.table[r.first + blockIdx.z];
-  const FieldShape s = field_shape(mem.n, mem.n);
-  if ((int)blockIdx.x >= s.columns || (int)blockIdx.y >= s.splits) return;  // the whole workgroup: another, larger member's
-  const size_t rel = (size_t)(mem.out_off - r.table[r.first].out_off);     // the bodies of the range before this member
-  jerk_body<T>(r.posm + mem.pos_off, r.velm + mem.vel_off, mem.n, s.tiles_per_split, r.parts + 2 * rel * gridDim.y, blockIdx.x, blockIdx.y);
+  const MemberGroup<JerkMember> g = member_group(r.table, r.first);
+  if (g.elsewhere()) return;
+  jerk_body<T>(r.posm + g.mem.pos_off, r.velm + g.mem.vel_off, g.mem.n, g.shape.tiles_per_split, r.parts + 2 * g.rel() * gridDim.y,
+               blockIdx.x, blockIdx.y);
 }
 
-// Body idx of the call's `total` bodies.  table == nullptr: every system has n_all bodies, member idx / n_all of the range.
-// Otherwise the member is the last of table[first .. first + count) whose out_off, taken from member first, is not above idx.
-// The member has field_shape(n, n).splits rows of n record pairs; its rows begin at (the bodies of the range before it) *
-// row_splits pairs, row_splits the gridDim.y of the pair-work launch.  Writes records 2 * idx and 2 * idx + 1 of out.
+// Body idx of the call's `total` bodies, its member found by member_at..  The member has field_shape(n, n).splits rows of n
+// record pairs; its rows begin at (the bodies of the range before it) * row_splits pairs, row_splits the gridDim.y of the
+// pair-work launch..  Writes records 2 * idx and 2 * idx + 1 of out.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void jerk_finish_kernel(const typename V4<T>::type* __restrict__ parts, const JerkMember* __restrict__ table,
                                                              unsigned first, int count, int n_all, int row_splits, unsigned total,
@@ -292,21 +258,9 @@ __global__ __launch_bounds__(kBlock) void jerk_finish_kernel(const typename V4<T
   using T4 = typename V4<T>::type;
   const unsigned idx = blockIdx.x * (unsigned)kBlock + threadIdx.x;
   if (idx >= total) return;
-  int n = n_all;
-  size_t rel = 0;  // the bodies of the range before the body's member
-  if (table) {
-    const unsigned long long base = table[first].out_off;
-    int lo = 0, hi = count - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (table[first + mid].out_off - base <= idx) lo = mid;
-      else hi = mid - 1;
-    }
-    n = table[first + lo].n;
-    rel = (size_t)(table[first + lo].out_off - base);
-  } else {
-    rel = (size_t)(idx / (unsigned)n_all) * (size_t)n_all;
-  }
+  const MemberAt at = member_at(table, first, count, n_all, idx);
+  const int n = at.n;
+  const size_t rel = at.rel;  // the bodies of the range before the body's member
   const int splits = field_shape(n, n).splits;
   const T4* row = parts + 2 * (rel * (size_t)row_splits + ((size_t)idx - rel));
   double ax = 0.0, ay = 0.0, az = 0.0, jx = 0.0, jy = 0.0, jz = 0.0;

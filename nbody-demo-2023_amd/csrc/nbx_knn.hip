@@ -119,7 +119,7 @@ int knn_members_t(nbx_ragged* r, const char* where, int first, int count, int k,
   using T4 = typename V4<T>::type;
   std::vector<KnnMember> table;  // lives until run_knn has synchronised
   const int rc = ragged_member_table<KnnMember>(r, &r->knn_tab, &table, where, [](const MemberSpan& mem, unsigned long long out_off) {
-    return KnnMember{(unsigned long long)mem.pos_off, out_off, mem.n, 0};
+    return KnnMember{{(unsigned long long)mem.pos_off, out_off, mem.n, 0}};
   });
   if (rc) return rc;
   const GridExtents g = ragged_extents(r, first, count);

@@ -41,6 +41,7 @@
 
 #include "nbx_field_shape.hpp"
 #include "nbx_pair.hpp"
+#include "nbx_tilewalk.hpp"
 
 namespace nbx {
 
@@ -78,15 +79,6 @@ __device__ __forceinline__ void knn_insert(const T c, const int jg, T (&r)[K], i
   }
 }
 
-// A tile record, read whole.  The pair needs the three coordinates alone, and left to itself the compiler narrows the fp32 read
-// to 12 bytes, which occupies the LDS twice as long as the 16-byte read: the empty statement keeps .w alive and costs no
-// instruction.
-__device__ __forceinline__ float4 knn_record(const float4* tile, const int j) {
-  const float4 r = tile[j];
-  asm volatile("" ::"v"(r.w));
-  return r;
-}
-
 // One LDS tile against the lane's B bodies (j_glob: global index of tile record 0).  MASK: a pair may be the body itself or a
 // record at or beyond n.
 template <typename T, int K, int B, bool MASK>
@@ -97,7 +89,7 @@ __device__ __forceinline__ void knn_tile(const typename V4<T>::type* tile, const
     const f32x2 e2 = {softening2<float>(), softening2<float>()};
 #pragma unroll 4
     for (int j = 0; j < kTile; ++j) {
-      const float4 rec = knn_record(tile, j);
+      const float4 rec = whole_record(tile, j);
       const int jg = j_glob + j;
       const f32x2 dx = f32x2{rec.x, rec.x} - px, dy = f32x2{rec.y, rec.y} - py, dz = f32x2{rec.z, rec.z} - pz;
       f32x2 r2 = __builtin_elementwise_fma(dz, dz, e2);
@@ -147,8 +139,7 @@ __device__ __forceinline__ void knn_body(const typename V4<T>::type* __restrict_
   __shared__ T4 tile[kTile];
   const int t = threadIdx.x;
   const int l0 = col * (kBlock * B);  // first body of this workgroup
-  T4 zero;
-  zero.x = zero.y = zero.z = zero.w = (T)0;
+  const T4 zero = zero_record<T4>();
   T xi[B], yi[B], zi[B], r[B][K];
   int ig[B], jx[B][K];
 #pragma unroll
@@ -175,7 +166,7 @@ __device__ __forceinline__ void knn_body(const typename V4<T>::type* __restrict_
     __syncthreads();
     if (kt + 1 < k1) next = posm[(kt + 1) * kTile + t];
     const int j0 = kt * kTile;
-    if ((j0 < g_hi && j0 + kTile > g_lo) || j0 + kTile > n)
+    if (tile_masked(j0, g_lo, g_hi, n))
       knn_tile<T, K, B, true>(tile, j0, n, xi, yi, zi, ig, r, jx);
     else
       knn_tile<T, K, B, false>(tile, j0, n, xi, yi, zi, ig, r, jx);
@@ -219,13 +210,7 @@ __global__ __launch_bounds__(kBlock) void ensemble_knn_kernel(const EnsembleKnnA
                              e.parts + m * gridDim.y * (size_t)e.n * (size_t)e.k, blockIdx.x, blockIdx.y);
 }
 
-// one entry per member of a ragged ensemble, built on first use and fixed for the object's life
-struct KnnMember {
-  unsigned long long pos_off;  // the member's first record in posm
-  unsigned long long out_off;  // the bodies of the members before it: where its rows begin in a call that starts at member 0
-  int n;
-  int reserved;
-};
+struct KnnMember : OutMember {};
 
 template <typename T>
 struct RaggedKnnArgs {
@@ -246,33 +231,20 @@ __global__ __launch_bounds__(kBlock) void ragged_knn_kernel(const RaggedKnnArgs<
                              blockIdx.y);
 }
 
-// Body idx of the call's `total` bodies.  table == nullptr: every system has n_all bodies, member idx / n_all of the range.
-// Otherwise the member is the last of table[first .. first + count) whose out_off, taken from member first, is not above idx.
-// The member has field_shape(n, n).splits rows of n * k records; its rows begin at (the bodies of the range before it) *
-// row_splits * k, row_splits the gridDim.y of the pair-work launch.  The split rows are merged in ascending split order with
-// knn_insert: a row is ascending, so it is left at its first entry that is not below the list's last; a later split's j are
-// the higher ones and the compares are strict, so the merged list is in (r2, j) order.
+// Body idx of the call's `total` bodies, its member found by member_at..  The member has field_shape(n, n).splits rows of n * k
+// records; its rows begin at (the bodies of the range before it) * row_splits * k, row_splits the gridDim.y of the pair-work
+// launch..  The split rows are merged in ascending split order with knn_insert: a row is ascending, so it is left at its first
+// entry that is not below the list's last; a later split's j are the higher ones and the compares are strict, so the merged
+// list is in (r2, j) order.
 template <typename T, int K>
 __global__ __launch_bounds__(kBlock) void knn_finish_kernel(const KnnRecord<T>* __restrict__ parts, const KnnMember* __restrict__ table,
                                                             unsigned first, int count, int n_all, int row_splits, int k, unsigned total,
                                                             KnnRecord<T>* __restrict__ out) {
   const unsigned idx = blockIdx.x * (unsigned)kBlock + threadIdx.x;
   if (idx >= total) return;
-  int n = n_all;
-  size_t rel = 0;  // the bodies of the range before the body's member
-  if (table) {
-    const unsigned long long base = table[first].out_off;
-    int lo = 0, hi = count - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (table[first + mid].out_off - base <= idx) lo = mid;
-      else hi = mid - 1;
-    }
-    n = table[first + lo].n;
-    rel = (size_t)(table[first + lo].out_off - base);
-  } else {
-    rel = (size_t)(idx / (unsigned)n_all) * (size_t)n_all;
-  }
+  const MemberAt at = member_at(table, first, count, n_all, idx);
+  const int n = at.n;
+  const size_t rel = at.rel;  // the bodies of the range before the body's member
   const int splits = field_shape(n, n).splits;
   const KnnRecord<T>* row = parts + (rel * (size_t)row_splits + ((size_t)idx - rel)) * (size_t)k;
   T r[K];

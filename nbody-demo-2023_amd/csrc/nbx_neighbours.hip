@@ -114,7 +114,7 @@ int neighbours_members_t(nbx_ragged* r, const char* where, int first, int count,
   using T4 = typename V4<T>::type;
   std::vector<NbMember> table;  // lives until run_neighbours has synchronised
   const int rc = ragged_member_table<NbMember>(r, &r->nb_tab, &table, where, [](const MemberSpan& mem, unsigned long long out_off) {
-    return NbMember{(unsigned long long)mem.pos_off, out_off, mem.n, 0};
+    return NbMember{{(unsigned long long)mem.pos_off, out_off, mem.n, 0}};
   });
   if (rc) return rc;
   const GridExtents g = ragged_extents(r, first, count);

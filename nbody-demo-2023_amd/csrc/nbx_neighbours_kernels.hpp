@@ -35,6 +35,7 @@
 
 #include "nbx_field_shape.hpp"
 #include "nbx_pair.hpp"
+#include "nbx_tilewalk.hpp"
 
 namespace nbx {
 
@@ -71,15 +72,6 @@ __device__ __forceinline__ void nb_take(const T r2, const int jg, const int n, c
   if constexpr (COUNT) cnt += in ? 1 : 0;
 }
 
-// A tile record, read whole.  The pair needs the three coordinates alone, and left to itself the compiler narrows the fp32 read
-// to 12 bytes (ds_read_b96), which occupies the LDS twice as long as the 16-byte read (ds_read_b128): the empty statement keeps
-// .w alive and costs no instruction.
-__device__ __forceinline__ float4 nb_record(const float4* tile, const int j) {
-  const float4 r = tile[j];
-  asm volatile("" ::"v"(r.w));
-  return r;
-}
-
 // One LDS tile against the lane's B bodies (j_glob: global index of tile record 0).
 template <typename T, int B, bool MASK, bool COUNT>
 __device__ __forceinline__ void nb_tile(const typename V4<T>::type* tile, const int j_glob, const int n, const T (&xi)[B], const T (&yi)[B],
@@ -95,7 +87,7 @@ __device__ __forceinline__ void nb_tile(const typename V4<T>::type* tile, const 
     const f32x2 e2 = {softening2<float>(), softening2<float>()};
 #pragma unroll 4
     for (int j = 0; j < kTile; ++j) {
-      const float4 r = nb_record(tile, j);
+      const float4 r = whole_record(tile, j);
       const int jg = j_glob + j;
 #pragma unroll
       for (int h = 0; h < B / 2; ++h) {
@@ -132,8 +124,7 @@ __device__ __forceinline__ void nb_body(const typename V4<T>::type* __restrict__
   __shared__ T4 tile[kTile];
   const int t = threadIdx.x;
   const int l0 = col * (kBlock * B);  // first body of this workgroup
-  T4 zero;
-  zero.x = zero.y = zero.z = zero.w = (T)0;
+  const T4 zero = zero_record<T4>();
   T xi[B], yi[B], zi[B], best[B];
   int ig[B], bj[B], cnt[B];
 #pragma unroll
@@ -158,7 +149,7 @@ __device__ __forceinline__ void nb_body(const typename V4<T>::type* __restrict__
     __syncthreads();
     if (k + 1 < k1) next = posm[(k + 1) * kTile + t];
     const int j0 = k * kTile;
-    if ((j0 < g_hi && j0 + kTile > g_lo) || j0 + kTile > n)
+    if (tile_masked(j0, g_lo, g_hi, n))
       nb_tile<T, B, true, COUNT>(tile, j0, n, xi, yi, zi, ig, h2, best, bj, cnt);
     else
       nb_tile<T, B, false, COUNT>(tile, j0, n, xi, yi, zi, ig, h2, best, bj, cnt);
@@ -198,13 +189,7 @@ __global__ __launch_bounds__(kBlock) void ensemble_neighbour_kernel(const Ensemb
                                blockIdx.x, blockIdx.y);
 }
 
-// one entry per member of a ragged ensemble, built on first use and fixed for the object's life
-struct NbMember {
-  unsigned long long pos_off;  // the member's first record in posm
-  unsigned long long out_off;  // the bodies of the members before it: where its results begin in a call that starts at member 0
-  int n;
-  int reserved;
-};
+struct NbMember : OutMember {};
 
 template <typename T>
 struct RaggedNbArgs {
@@ -217,38 +202,24 @@ struct RaggedNbArgs {
 
 template <typename T, bool COUNT>
 __global__ __launch_bounds__(kBlock) void ragged_neighbour_kernel(const RaggedNbArgs<T> r) {
-  const NbMember mem = r.table[r.first + blockIdx.z];
-  const FieldShape s = field_shape(mem.n, mem.n);
-  if ((int)blockIdx.x >= s.columns || (int)blockIdx.y >= s.splits) return;  // the whole workgroup: another, larger member's
-  const size_t rel = (size_t)(mem.out_off - r.table[r.first].out_off);     // the bodies of the range before this member
-  nb_body<T, kNbBodies, COUNT>(r.posm + mem.pos_off, mem.n, s.tiles_per_split, r.h2, r.parts + rel * gridDim.y, blockIdx.x, blockIdx.y);
+  const MemberGroup<NbMember> g = member_group(r.table, r.first);
+  if (g.elsewhere()) return;
+  nb_body<T, kNbBodies, COUNT>(r.posm + g.mem.pos_off, g.mem.n, g.shape.tiles_per_split, r.h2, r.parts + g.rel() * gridDim.y, blockIdx.x,
+                               blockIdx.y);
 }
 
-// Body idx of the call's `total` bodies.  table == nullptr: every system has n_all bodies, member idx / n_all of the range.
-// Otherwise the member is the last of table[first .. first + count) whose out_off, taken from member first, is not above idx.
-// The member has field_shape(n, n).splits rows of n records; its rows begin at (the bodies of the range before it) * row_splits,
-// row_splits the gridDim.y of the pair-work launch.
+// Body idx of the call's `total` bodies, its member found by member_at..  The member has field_shape(n, n).splits rows of n
+// records; its rows begin at (the bodies of the range before it) * row_splits, row_splits the gridDim.y of the pair-work
+// launch.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void neighbour_finish_kernel(const NbRecord<T>* __restrict__ parts, const NbMember* __restrict__ table,
                                                                   unsigned first, int count, int n_all, int row_splits, unsigned total,
                                                                   NbRecord<T>* __restrict__ out) {
   const unsigned idx = blockIdx.x * (unsigned)kBlock + threadIdx.x;
   if (idx >= total) return;
-  int n = n_all;
-  size_t rel = 0;  // the bodies of the range before the body's member
-  if (table) {
-    const unsigned long long base = table[first].out_off;
-    int lo = 0, hi = count - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (table[first + mid].out_off - base <= idx) lo = mid;
-      else hi = mid - 1;
-    }
-    n = table[first + lo].n;
-    rel = (size_t)(table[first + lo].out_off - base);
-  } else {
-    rel = (size_t)(idx / (unsigned)n_all) * (size_t)n_all;
-  }
+  const MemberAt at = member_at(table, first, count, n_all, idx);
+  const int n = at.n;
+  const size_t rel = at.rel;  // the bodies of the range before the body's member
   const int splits = field_shape(n, n).splits;
   const NbRecord<T>* row = parts + rel * (size_t)row_splits + ((size_t)idx - rel);
   NbRecord<T> o;

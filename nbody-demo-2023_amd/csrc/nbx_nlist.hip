@@ -159,7 +159,7 @@ int nlist_members_t(nbx_ragged* r, const char* where, int first, int count, doub
   using T4 = typename V4<T>::type;
   std::vector<NlMember> table;  // lives until run_nlist has synchronised
   const int rc = ragged_member_table<NlMember>(r, &r->nl_tab, &table, where, [](const MemberSpan& mem, unsigned long long out_off) {
-    return NlMember{(unsigned long long)mem.pos_off, out_off, mem.n, 0};
+    return NlMember{{(unsigned long long)mem.pos_off, out_off, mem.n, 0}};
   });
   if (rc) return rc;
   const GridExtents g = ragged_extents(r, first, count);

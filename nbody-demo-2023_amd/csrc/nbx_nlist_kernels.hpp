@@ -34,6 +34,7 @@
 #include "nbx_field_shape.hpp"
 #include "nbx_nlist_shape.hpp"
 #include "nbx_pair.hpp"
+#include "nbx_tilewalk.hpp"
 
 namespace nbx {
 
@@ -80,13 +81,6 @@ __device__ __forceinline__ void nl_put(const bool in, const int jg, const T r2, 
   }
 }
 
-// A tile record, read whole (nb_record's reason: the 16-byte LDS read occupies the LDS half as long as the 12-byte one).
-__device__ __forceinline__ float4 nl_record(const float4* tile, const int j) {
-  const float4 r = tile[j];
-  asm volatile("" ::"v"(r.w));
-  return r;
-}
-
 // One LDS tile against the lane's B bodies (j_glob: index of tile record 0 in its system).
 template <typename T, int B, bool MASK, bool FILL>
 __device__ __forceinline__ void nl_tile(const typename V4<T>::type* tile, const int j_glob, const int n, const T (&xi)[B], const T (&yi)[B],
@@ -97,7 +91,7 @@ __device__ __forceinline__ void nl_tile(const typename V4<T>::type* tile, const 
     const f32x2 e2 = {softening2<float>(), softening2<float>()};
 #pragma unroll 4
     for (int j = 0; j < kTile; ++j) {
-      const float4 r = nl_record(tile, j);
+      const float4 r = whole_record(tile, j);
       const int jg = j_glob + j;
       const f32x2 dx = f32x2{r.x, r.x} - px, dy = f32x2{r.y, r.y} - py, dz = f32x2{r.z, r.z} - pz;
       f32x2 r2 = __builtin_elementwise_fma(dz, dz, e2);
@@ -150,8 +144,7 @@ __device__ __forceinline__ void nl_body(const typename V4<T>::type* __restrict__
   __shared__ T4 tile[kTile];
   const int t = threadIdx.x;
   const int l0 = col * (kBlock * B);  // first body of this workgroup
-  T4 zero;
-  zero.x = zero.y = zero.z = zero.w = (T)0;
+  const T4 zero = zero_record<T4>();
   T xi[B], yi[B], zi[B];
   int ig[B], cnt[B];
   unsigned pos[B], end[B];
@@ -223,13 +216,7 @@ __global__ __launch_bounds__(kBlock) void ensemble_nlist_kernel(const EnsembleNl
                               blockIdx.x, blockIdx.y);
 }
 
-// one entry per member of a ragged ensemble, built on first use and fixed for the object's life
-struct NlMember {
-  unsigned long long pos_off;  // the member's first record in posm
-  unsigned long long out_off;  // the bodies of the members before it: where its bodies begin in a call that starts at member 0
-  int n;
-  int reserved;
-};
+struct NlMember : OutMember {};
 
 template <typename T>
 struct RaggedNlArgs {
@@ -242,39 +229,26 @@ struct RaggedNlArgs {
 
 template <typename T, bool FILL>
 __global__ __launch_bounds__(kBlock) void ragged_nlist_kernel(const RaggedNlArgs<T> r, const NlLists<T> out) {
-  const NlMember mem = r.table[r.first + blockIdx.z];
-  const FieldShape s = field_shape(mem.n, mem.n);
-  if ((int)blockIdx.x >= s.columns || (int)blockIdx.y >= s.splits) return;  // the whole workgroup: another, larger member's
-  const size_t rel = (size_t)(mem.out_off - r.table[r.first].out_off);     // the bodies of the range before this member
+  const MemberGroup<NlMember> g = member_group(r.table, r.first);
+  if (g.elsewhere()) return;
+  const size_t rel = g.rel();
   NlLists<T> mine = out;
   mine.offsets = out.offsets + rel;
-  nl_body<T, kNlBodies, FILL>(r.posm + mem.pos_off, mem.n, s.tiles_per_split, r.h2, r.seg + rel * gridDim.y, mine, blockIdx.x, blockIdx.y);
+  nl_body<T, kNlBodies, FILL>(r.posm + g.mem.pos_off, g.mem.n, g.shape.tiles_per_split, r.h2, r.seg + rel * gridDim.y, mine, blockIdx.x,
+                              blockIdx.y);
 }
 
-// Body idx of the call's `total` bodies.  table == nullptr: every system has n_all bodies, member idx / n_all of the range.
-// Otherwise the member is the last of table[first .. first + count) whose out_off, taken from member first, is not above idx.
-// The member has field_shape(n, n).splits rows of n segments; its rows begin at (the bodies of the range before it) * row_splits,
-// row_splits the gridDim.y of the pair-work launch.
+// Body idx of the call's `total` bodies, its member found by member_at..  The member has field_shape(n, n).splits rows of n
+// segments; its rows begin at (the bodies of the range before it) * row_splits, row_splits the gridDim.y of the pair-work
+// launch.
 __global__ __launch_bounds__(kBlock) void nlist_finish_kernel(NlSegment* __restrict__ seg, const NlMember* __restrict__ table, unsigned first,
                                                               int count, int n_all, int row_splits, unsigned total,
                                                               long long* __restrict__ within) {
   const unsigned idx = blockIdx.x * (unsigned)kBlock + threadIdx.x;
   if (idx >= total) return;
-  int n = n_all;
-  size_t rel = 0;  // the bodies of the range before the body's member
-  if (table) {
-    const unsigned long long base = table[first].out_off;
-    int lo = 0, hi = count - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (table[first + mid].out_off - base <= idx) lo = mid;
-      else hi = mid - 1;
-    }
-    n = table[first + lo].n;
-    rel = (size_t)(table[first + lo].out_off - base);
-  } else {
-    rel = (size_t)(idx / (unsigned)n_all) * (size_t)n_all;
-  }
+  const MemberAt at = member_at(table, first, count, n_all, idx);
+  const int n = at.n;
+  const size_t rel = at.rel;  // the bodies of the range before the body's member
   const int splits = field_shape(n, n).splits;
   NlSegment* row = seg + rel * (size_t)row_splits + ((size_t)idx - rel);
   int sum = 0;  // below n <= 2^22

@@ -153,7 +153,7 @@ int paircount_members_t(nbx_ragged* r, const char* where, int first, int count, 
   using T4 = typename V4<T>::type;
   std::vector<PcMember> table;  // lives until run_paircount has synchronised
   int rc = ragged_member_table<PcMember>(r, &r->pc_tab, &table, where, [](const MemberSpan& mem, unsigned long long) {
-    return PcMember{(unsigned long long)mem.pos_off, mem.n, 0};
+    return PcMember{{(unsigned long long)mem.pos_off, mem.n, 0}};
   });
   if (rc) return rc;
   const GridExtents g = ragged_extents(r, first, count);

@@ -38,6 +38,7 @@
 
 #include "nbx_field_shape.hpp"
 #include "nbx_pair.hpp"
+#include "nbx_tilewalk.hpp"
 
 namespace nbx {
 
@@ -82,14 +83,6 @@ __device__ __forceinline__ void pc_take(const T r2, const bool ok, const PcRadii
   }
 }
 
-// A tile record, read whole (nb_record's reason: left to itself the compiler narrows the fp32 read to 12 bytes, which occupies
-// the LDS twice as long as the 16-byte read).
-__device__ __forceinline__ float4 pc_record(const float4* tile, const int j) {
-  const float4 r = tile[j];
-  asm volatile("" ::"v"(r.w));
-  return r;
-}
-
 // One LDS tile against the lane's two bodies (j_glob: global index of tile record 0).
 template <typename T, int E, bool MASK, bool WAVE>
 __device__ __forceinline__ void pc_tile(const typename V4<T>::type* tile, const int j_glob, const int n, const T (&xi)[kPcBodies],
@@ -100,7 +93,7 @@ __device__ __forceinline__ void pc_tile(const typename V4<T>::type* tile, const 
     const f32x2 e2 = {softening2<float>(), softening2<float>()};
 #pragma unroll kPcUnroll<E>
     for (int j = 0; j < kTile; ++j) {
-      const float4 r = pc_record(tile, j);
+      const float4 r = whole_record(tile, j);
       const int jg = j_glob + j;
       const f32x2 dx = f32x2{r.x, r.x} - px, dy = f32x2{r.y, r.y} - py, dz = f32x2{r.z, r.z} - pz;
       f32x2 r2 = __builtin_elementwise_fma(dz, dz, e2);
@@ -134,8 +127,7 @@ __device__ __forceinline__ void pc_body(const typename V4<T>::type* __restrict__
   __shared__ unsigned red[kBlock / 64][E];
   const int t = threadIdx.x;
   const int l0 = col * (kBlock * kPcBodies);  // first body of this workgroup
-  T4 zero;
-  zero.x = zero.y = zero.z = zero.w = (T)0;
+  const T4 zero = zero_record<T4>();
   T xi[kPcBodies], yi[kPcBodies], zi[kPcBodies];
   int ig[kPcBodies];
   unsigned cnt[E];
@@ -215,12 +207,7 @@ __global__ __launch_bounds__(kBlock) void ensemble_paircount_kernel(const Ensemb
                       pc_out(e.parts, (size_t)e.member_stride), blockIdx.x, blockIdx.y);
 }
 
-// one entry per member of a ragged ensemble, built on first use and fixed for the object's life
-struct PcMember {
-  unsigned long long pos_off;  // the member's first record in posm
-  int n;
-  int reserved;
-};
+struct PcMember : PosMember {};
 
 template <typename T, int E>
 struct RaggedPcArgs {

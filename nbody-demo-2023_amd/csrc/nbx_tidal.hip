@@ -132,7 +132,7 @@ int tidal_members_t(nbx_ragged* r, const char* where, int first, int count, int 
   using T4 = typename V4<T>::type;
   std::vector<TidalMember> table;  // lives until run_tidal has synchronised
   const int rc = ragged_member_table<TidalMember>(r, &r->tidal_tab, &table, where, [](const MemberSpan& mem, unsigned long long out_off) {
-    return TidalMember{(unsigned long long)mem.pos_off, out_off, mem.n, 0};
+    return TidalMember{{(unsigned long long)mem.pos_off, out_off, mem.n, 0}};
   });
   if (rc) return rc;
   const GridExtents g = ragged_extents(r, first, count, p ? m : 0);

@@ -42,6 +42,7 @@
 
 #include "nbx_field_shape.hpp"
 #include "nbx_pair.hpp"
+#include "nbx_tilewalk.hpp"
 
 namespace nbx {
 
@@ -175,8 +176,7 @@ __device__ __forceinline__ void tidal_body(const typename V4<T>::type* __restric
   __shared__ T4 tile[kTile];
   const int t = threadIdx.x;
   const int l0 = col * (kBlock * B);  // first point of this workgroup
-  T4 zero;
-  zero.x = zero.y = zero.z = zero.w = (T)0;
+  const T4 zero = zero_record<T4>();
   TidalLane<T> lane;
 #pragma unroll
   for (int b = 0; b < B; ++b) {
@@ -186,15 +186,9 @@ __device__ __forceinline__ void tidal_body(const typename V4<T>::type* __restric
     lane.load(b, p);
   }
   lane.clear();
-  const int tiles = (n + kTile - 1) / kTile;
-  const int k0 = split * tiles_per_split, k1 = min(tiles, k0 + tiles_per_split);
-  T4 next = zero;
-  if (k0 < k1) next = posm[k0 * kTile + t];
-  for (int k = k0; k < k1; ++k) {
-    __syncthreads();  // every lane is done with the previous tile
-    tile[t] = next;
-    __syncthreads();
-    if (k + 1 < k1) next = posm[(k + 1) * kTile + t];
+  TileWalk<T4> walk(posm, n, split, tiles_per_split);
+  for (int k = walk.k0; k < walk.k1; ++k) {
+    walk.stage(tile, k);
     if (BODIES && k == B * col) lane.template tile<0>(tile);
     else if (BODIES && k == B * col + 1) lane.template tile<1>(tile);
     else lane.template tile<-1>(tile);
@@ -242,13 +236,7 @@ __global__ __launch_bounds__(kBlock) void ensemble_tidal_kernel(const EnsembleTi
                                       e.parts + 2 * k * gridDim.y * (size_t)m, blockIdx.x, blockIdx.y);
 }
 
-// one entry per member of a ragged ensemble, built on first use and fixed for the object's life
-struct TidalMember {
-  unsigned long long pos_off;  // the member's first record in posm
-  unsigned long long out_off;  // the bodies of the members before it: where its bodies-mode results begin in a call from member 0
-  int n;
-  int reserved;
-};
+struct TidalMember : OutMember {};
 
 template <typename T>
 struct RaggedTidalArgs {
@@ -263,23 +251,20 @@ struct RaggedTidalArgs {
 template <typename T, bool BODIES>
 __global__ __launch_bounds__(kBlock) void ragged_tidal_kernel(const RaggedTidalArgs<T> r) {
   const size_t k = blockIdx.z;
-  const TidalMember mem = r.table[r.first + k];
-  const int m = BODIES ? mem.n : r.m;
-  const FieldShape s = field_shape(m, mem.n);
-  if ((int)blockIdx.x >= s.columns || (int)blockIdx.y >= s.splits) return;  // the whole workgroup: another, larger member's
-  const typename V4<T>::type* posm = r.posm + mem.pos_off;
-  // the points or bodies of the range before this member
-  const size_t rel = BODIES ? (size_t)(mem.out_off - r.table[r.first].out_off) : k * (size_t)m;
-  tidal_body<T, BODIES>(posm, mem.n, BODIES ? posm : r.pts + rel, m, s.tiles_per_split, r.parts + 2 * rel * gridDim.y,
+  const MemberGroup<TidalMember> g = member_group(r.table, r.first, BODIES ? 0 : r.m);
+  if (g.elsewhere()) return;
+  const int m = BODIES ? g.mem.n : r.m;
+  const typename V4<T>::type* posm = r.posm + g.mem.pos_off;
+  const size_t rel = BODIES ? g.rel() : k * (size_t)m;  // the points or bodies of the range before this member
+  tidal_body<T, BODIES>(posm, g.mem.n, BODIES ? posm : r.pts + rel, m, g.shape.tiles_per_split, r.parts + 2 * rel * gridDim.y,
                                       blockIdx.x, blockIdx.y);
 }
 
-// Point or body idx of the call's `total`.  m > 0, points mode: member idx / m of the range, point idx % m; the member has n
-// bodies from the table (a ragged ensemble) or n_all (table == nullptr).  m == 0, bodies mode: table == nullptr: member
-// idx / n_all; otherwise the member is the last of table[first .. first + count) whose out_off, taken from member first, is not
-// above idx.  A system of `pts` points has field_shape(pts, n).splits rows of pts record pairs; its rows begin at (the points of
-// the range before it) * row_splits pairs, row_splits the gridDim.y of the pair-work launch.  Writes records 2 * idx
-// {xx, xy, xz, yy} and 2 * idx + 1 {yz, zz, 0, 0} of out.
+// Point or body idx of the call's `total`..  m > 0, points mode: member idx / m of the range, point idx % m; the member has n
+// bodies from the table (a ragged ensemble) or n_all (table == nullptr)..  m == 0, bodies mode: the member found by member_at..  A
+// system of `pts` points has field_shape(pts, n).splits rows of pts record pairs; its rows begin at (the points of the range
+// before it) * row_splits pairs, row_splits the gridDim.y of the pair-work launch..  Writes records 2 * idx {xx, xy, xz, yy} and
+// 2 * idx + 1 {yz, zz, 0, 0} of out.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void tidal_finish_kernel(const typename V4<T>::type* __restrict__ parts,
                                                               const TidalMember* __restrict__ table, unsigned first, int count, int n_all,
@@ -294,19 +279,10 @@ __global__ __launch_bounds__(kBlock) void tidal_finish_kernel(const typename V4<
     const unsigned k = idx / (unsigned)m;
     if (table) n = table[first + k].n;
     rel = (size_t)k * (size_t)m;
-  } else if (table) {
-    const unsigned long long base = table[first].out_off;
-    int lo = 0, hi = count - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (table[first + mid].out_off - base <= idx) lo = mid;
-      else hi = mid - 1;
-    }
-    n = pts = table[first + lo].n;
-    rel = (size_t)(table[first + lo].out_off - base);
   } else {
-    pts = n_all;
-    rel = (size_t)(idx / (unsigned)n_all) * (size_t)n_all;
+    const MemberAt at = member_at(table, first, count, n_all, idx);
+    n = pts = at.n;
+    rel = at.rel;
   }
   const int splits = field_shape(pts, n).splits;
   const T4* row = parts + 2 * (rel * (size_t)row_splits + ((size_t)idx - rel));

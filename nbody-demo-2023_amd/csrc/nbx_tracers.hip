@@ -149,7 +149,7 @@ int ensure_table(nbx_ensemble*, const char*, std::vector<TracerMember>*) { retur
 // `table` lives until the caller has synchronised
 int ensure_table(nbx_ragged* r, const char* where, std::vector<TracerMember>* table) {
   return ragged_member_table<TracerMember>(r, &r->tr_tab, table, where, [](const MemberSpan& mem, unsigned long long) {
-    return TracerMember{(unsigned long long)mem.pos_off, mem.n, 0};
+    return TracerMember{{(unsigned long long)mem.pos_off, mem.n, 0}};
   });
 }
 

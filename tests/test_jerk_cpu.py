@@ -250,7 +250,9 @@ def test_the_kernels_live_in_their_own_translation_unit_reuse_the_shape_rule_and
     assert "atomic" not in both
     assert "__shared__ T4 ptile[kTile];" in kern and "__shared__ T4 vtile[kTile];" in kern  # two arrays per tile
     code = re.sub(r"//.*", "", kern)
-    assert code.count("velm[j]") == 2 and len(re.findall(r"if \(j < n\) next_v = velm\[j\];", code)) == 2  # only below n
+    walk = re.sub(r"//.*", "", open(os.path.join(CSRC, "nbx_tilewalk.hpp")).read())  # the two-array walk lives in the shared device layer
+    assert "TileWalk2<T4> walk(posm, velm, n, split, tiles_per_split);" in code and "velm[j]" not in code
+    assert walk.count("velm[j]") == 2 and len(re.findall(r"if \(j < n\) next_v = velm\[j\];", walk)) == 2  # only below n
     assert code.count("velm[li]") == 1 and "if (li < n) {\n      p = posm[li];\n      v = velm[li];" in code
     for fn in ("check_range(", "check_uploaded(", "guarded(", "use_device(", "ensure_bytes(", "ragged_member_table<", "ragged_extents(", "read_back("):
         assert fn in src, fn

@@ -266,8 +266,13 @@ def test_the_kernels_live_in_their_own_translation_unit_reuse_the_shape_rule_and
     assert "static_assert(nl_scan_blocks(kNlMaxBodies) <= kNlScanBlock" in shape
     # no atomics, and no kernel waits for another workgroup: no flag is polled, nothing is volatile, no fence, no cooperative launch
     for word in ("atomic", "volatile(", "volatile ", "__threadfence", "cooperative", "while (", "__builtin_amdgcn_s_sleep"):
-        assert word not in both.replace('asm volatile("" ::"v"(r.w));', "").replace("while (lo < hi)", ""), word
-    assert both.count("while (") == 1  # the finish kernel's binary search over the member table
+        assert word not in both, word
+    # the whole-record read and the finish kernel's binary search over the member table live in the shared device layer
+    shared = re.sub(r"//.*", "", open(os.path.join(CSRC, "nbx_tilewalk.hpp")).read())
+    assert "whole_record(tile, j)" in kern and "member_at(table, first, count, n_all, idx)" in kern
+    assert shared.count('asm volatile("" ::"v"(r.w));') == 1 and shared.count("while (") == 1 and "while (lo < hi)" in shared
+    for word in ("atomic", "volatile ", "__threadfence", "cooperative", "__builtin_amdgcn_s_sleep"):
+        assert word not in shared.replace('asm volatile("" ::"v"(r.w));', ""), word
     # one pair function decides for both passes, and every store of the fill is behind the wave-wide branch and the segment's end
     assert both.count("r2 <= h2") == 1 and both.count("nl_in<") == 3
     assert "if (__any(in0 || in1)) {" in kern and "if (__any(some)) {" in kern and "if (pos < end) {" in kern
